@@ -19,6 +19,12 @@ kernel itself.  value = (S summed over ranks) * steps / (max-over-ranks time).
 N > 1 (torchrun, one process per GPU): screen-tile split — every rank owns a
 replica of the volume, renders its interleaved 32x32 tiles, rank 0 gathers the
 packed tiles over RCCL and unpacks them (that gather is inside the timed region).
+
+A plain run sets up, warms up, times the steps and prints the result line.  --full
+adds what takes runs of its own: the kernel-time pass and the roofline, the plugin
+cadence, the CPU baseline with the parity of the frame against the oracle, and at
+N > 1 the check of the gathered frame.  --dump-outputs DIR writes the last timed
+frame as DIR/frame.npy.
 """
 from __future__ import annotations
 
@@ -198,8 +204,18 @@ def parse(argv=None):
                         "(-1: the library default, 3: + the distance skip when every lane can)")
     p.add_argument("--batch", type=int, default=0, choices=[0, 2, 4],
                    help="rc1pass samples per lane per memory round trip (0 = auto: 4, 2 with Phong)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the kernel-time "
+                        "pass and the roofline, the plugin cadence, the CPU baseline and the "
+                        "parity of the frame against the oracle, at N > 1 the check of the "
+                        "gathered frame")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the frame of the last timed step to "
+                        "DIR/frame.npy (float32; a seeded sample of the pixels, (K, 4), when "
+                        "the frame exceeds 32 MiB)")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full without the CPU baseline and the parity block")
     p.add_argument("--format", choices=["rgba16f", "rgba32f"], default="rgba16f",
                    help="frame format: RGBA16F (the reference's framebuffer) or RGBA32F")
     p.add_argument("--hw-queues", type=int, default=0,
@@ -238,7 +254,7 @@ def parse(argv=None):
     p.add_argument("--postpass", action="store_true",
                    help="also time the multiscaling post-pass filters on this workload's frame")
     p.add_argument("--no-cadence", action="store_true",
-                   help="rc1pass, 1 GPU: skip the plugin-cadence lines (one frame per call on one "
+                   help="--full, rc1pass, 1 GPU: skip the plugin-cadence lines (one frame per call on one "
                         "stream: the static view and the 24-state orbit)")
     p.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_rc1pass.json"))
     p.add_argument("--orbit", action="store_true",
@@ -466,6 +482,23 @@ def lib_sha16():
         return hashlib.sha256(f.read()).hexdigest()[:16]
 
 
+DUMP_FULL_BYTES = 32 << 20
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the frame of the last timed step (rank 0's image, what a caller of
+    the timed path receives) as float32 in `path`/frame.npy.  A frame above 32 MiB (the
+    2048^2 DOS frame) is written as a fixed sample of 2^21 of its pixels, (K, 4), drawn
+    with seed 0 and sorted, so two builds sample the same pixels."""
+    os.makedirs(path, exist_ok=True)
+    img = image.float().cpu().numpy()
+    if img.nbytes > DUMP_FULL_BYTES:
+        px = img.reshape(-1, img.shape[-1])
+        keep = np.random.default_rng(0).choice(px.shape[0], DUMP_FULL_BYTES // 16, replace=False)
+        img = px[np.sort(keep)]
+    np.save(os.path.join(path, "frame.npy"), np.ascontiguousarray(img, dtype=np.float32))
+
+
 def load_pmc(path, workload_key, kernel, sha):
     """The PMC record (tools/pmc_record.py) of this exact workload, dominant kernel and
     library build: `path` or any profiles/pmc_<renderer>*.json beside it; {} if none.
@@ -651,7 +684,7 @@ def main():
     if ebs and a.sat_layout >= 0:
         N.check(N.lib().cvr_set_option(r.device.handle, b"sat_layout", a.sat_layout), "sat_layout",
                 r.device.handle)
-    if ebs:
+    if ebs and a.full:
         # the SAT precompute on its own (Init built it once already): GPU wall time
         torch.cuda.synchronize()
         t_sat = time.perf_counter()
@@ -775,8 +808,9 @@ def main():
 
     # samples per frame (this rank) and camera, counted by the kernel; for the shaded
     # renderers also the shaded / shadow-lit samples and the secondary fetches
-    # (rc1pass: [0] Phong-shaded samples, [1] samples the per-cell skip stepped over)
-    count_shaded = not iso
+    # (rc1pass: [0] Phong-shaded samples, [1] samples the per-cell skip stepped over);
+    # only the roofline reads those, so a plain run counts the samples alone
+    count_shaded = a.full and not iso
     if count_shaded:
         N.check(L.cvr_set_option(r.device.handle, b"shade_counters", 1), "opt", r.device.handle)
     S_cam = []
@@ -833,10 +867,13 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
 
-    # multi-GPU check: rank 0 renders the whole frame itself; the gathered image
-    # must equal it bit for bit
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, split.image)
+
+    # multi-GPU check (--full): rank 0 renders the whole frame itself; the gathered
+    # image must equal it bit for bit
     split_exact = None
-    if world > 1 and rank == 0:
+    if a.full and world > 1 and rank == 0:
         full = torch.zeros_like(split.image)
         last_cam = cams[(a.steps - 1) % len(cams)]
         r.render_to(make_frame(last_cam, W, H), N.Output(full.data_ptr(), None, None, 1, fmt))
@@ -844,49 +881,51 @@ def main():
         split_exact = bool(torch.equal(full.view(torch.int16 if fmt else torch.int32),
                                        split.image.view(torch.int16 if fmt else torch.int32)))
 
-    # Kernel-only time for the roofline: HIP events the library records on its
+    # Kernel-only time for the roofline (--full): HIP events the library records on its
     # own stream around the ray-march launch (kernel_timing), in a separate pass.
     # With multi-frame launches the pass times the same launches as the timed region:
     # floor(steps / FPL) launches of FPL frames (the roofline's bytes are per launch).
-    n_launch = max(1, a.steps // FPL)
-    N.check(L.cvr_set_option(r.device.handle, b"kernel_timing", n_launch if renders else 0),
-            "kernel_timing", r.device.handle)
-    total.zero_()
-    if not renders:
-        S_timed = 0
-    elif FPL > 1:
-        mf_bufs = [out_buf] + [torch.empty_like(out_buf) for _ in range(FPL - 1)]
-        mf_outs = [N.Output(mf_bufs[j].data_ptr(), None, total.data_ptr() if j == 0 else None, 1, fmt)
-                   for j in range(FPL)]
-        for k in range(n_launch):
-            r.render_frames_to([frames[(k * FPL + j) % len(frames)] for j in range(FPL)], mf_outs)
-        S_timed = sum(S_cam[i % len(S_cam)] for i in range(n_launch * FPL))
-    else:
-        for i in range(a.steps):
-            step_once(i)
-        S_timed = S_rank_steps
-    torch.cuda.synchronize(dev)
-    kern_ms = 0.0
-    if renders:
-        kt = (ctypes.c_float * n_launch)()
-        nkt = ctypes.c_int()
-        N.check(L.cvr_read_kernel_times(r.device.handle, kt, n_launch, ctypes.byref(nkt)),
-                "cvr_read_kernel_times", r.device.handle)
-        assert nkt.value == n_launch
-        kern_ms = float(np.mean(kt[:nkt.value]))
-    assert int(total.item()) == S_timed, "sample count changed between frames"
-    S_launch = int(round(S_timed / n_launch))            # samples per launch (FPL frames)
-    roof_src = "this rank"
-    if world > 1 and split.idle_root:
-        # an idle root renders nothing: the roofline is rank 1's share (same launches)
-        v = torch.tensor([kern_ms, S_launch, pixels, shade[0], shade[1], shade[2]],
-                         dtype=torch.float64, device=dev)
-        dist.broadcast(v, src=1)
-        kern_ms, S_launch, pixels = float(v[0]), int(v[1]), int(v[2])
-        for q in range(3):
-            shade[q] = int(v[3 + q])
-        roof_src = "rank 1 (rank 0 only gathers)"
-    batch = L.cvr_get_option(r.device.handle, b"batch") or (2 if a.phong else 4)   # 0 = auto
+    if a.full:
+        n_launch = max(1, a.steps // FPL)
+        N.check(L.cvr_set_option(r.device.handle, b"kernel_timing", n_launch if renders else 0),
+                "kernel_timing", r.device.handle)
+        total.zero_()
+        if not renders:
+            S_timed = 0
+        elif FPL > 1:
+            mf_bufs = [out_buf] + [torch.empty_like(out_buf) for _ in range(FPL - 1)]
+            mf_outs = [N.Output(mf_bufs[j].data_ptr(), None, total.data_ptr() if j == 0 else None,
+                                1, fmt) for j in range(FPL)]
+            for k in range(n_launch):
+                r.render_frames_to([frames[(k * FPL + j) % len(frames)] for j in range(FPL)],
+                                   mf_outs)
+            S_timed = sum(S_cam[i % len(S_cam)] for i in range(n_launch * FPL))
+        else:
+            for i in range(a.steps):
+                step_once(i)
+            S_timed = S_rank_steps
+        torch.cuda.synchronize(dev)
+        kern_ms = 0.0
+        if renders:
+            kt = (ctypes.c_float * n_launch)()
+            nkt = ctypes.c_int()
+            N.check(L.cvr_read_kernel_times(r.device.handle, kt, n_launch, ctypes.byref(nkt)),
+                    "cvr_read_kernel_times", r.device.handle)
+            assert nkt.value == n_launch
+            kern_ms = float(np.mean(kt[:nkt.value]))
+        assert int(total.item()) == S_timed, "sample count changed between frames"
+        S_launch = int(round(S_timed / n_launch))            # samples per launch (FPL frames)
+        roof_src = "this rank"
+        if world > 1 and split.idle_root:
+            # an idle root renders nothing: the roofline is rank 1's share (same launches)
+            v = torch.tensor([kern_ms, S_launch, pixels, shade[0], shade[1], shade[2]],
+                             dtype=torch.float64, device=dev)
+            dist.broadcast(v, src=1)
+            kern_ms, S_launch, pixels = float(v[0]), int(v[1]), int(v[2])
+            for q in range(3):
+                shade[q] = int(v[3 + q])
+            roof_src = "rank 1 (rank 0 only gathers)"
+        batch = L.cvr_get_option(r.device.handle, b"batch") or (2 if a.phong else 4)   # 0 = auto
     macro = L.cvr_get_option(r.device.handle, b"macro")
 
     if world > 1:
@@ -903,6 +942,12 @@ def main():
     if rank == 0:
         msps = S_all_steps / elapsed / 1e6
         ms_per_step = elapsed / a.steps * 1e3
+        wkey = (f"{a.renderer}_{a.field}{n}_{W}x{H}{'_phong' if a.phong else ''}"
+                f"{'_orbit' if a.orbit else ''}"
+                f"{f'_alpha{a.tf_alpha:g}' if a.tf_alpha != 1.0 else ''}")
+        sha = lib_sha16()
+    roof = None
+    if rank == 0 and a.full:
         # algorithmic bytes per launch: 8 trilinear corners x 1 B (u8 input)
         # per sample + the output pixel (RGBA16F 8 B, RGBA32F 16 B) (+ 48 B per shaded
         # sample for the Phong gradient: 8 corners x 3 fp16, counted by the kernel)
@@ -924,9 +969,6 @@ def main():
             # + 8 float corners (32 B) per trilinear SAT fetch
             b_alg += 32 * fetches
         achieved = b_alg / (kern_ms * 1e-3) / 1e9
-        wkey = (f"{a.renderer}_{a.field}{n}_{W}x{H}{'_phong' if a.phong else ''}"
-                f"{'_orbit' if a.orbit else ''}"
-                f"{f'_alpha{a.tf_alpha:g}' if a.tf_alpha != 1.0 else ''}")
         flat = shaded and N.lib().cvr_get_option(r.device.handle, b"shade_flat") == 1
         kname = ("flat_shade_kernel<DosShader> (+ shaded_jobs_kernel x2, flat_fold_kernel)" if dos and flat else
                  "flat_shade_kernel<EbsShaderT> (+ shaded_jobs_kernel x2, flat_fold_kernel)" if ebs and flat else
@@ -939,7 +981,6 @@ def main():
         # pipe from L1/L2/MALL, far above what HBM could serve at these frame times:
         # their roofline is the L2's, with the HBM figures (PMC traffic) beside it
         peak = L2_PEAK_GBS if shaded else HBM_PEAK_GBS
-        sha = lib_sha16()
         pmc = load_pmc(a.pmc.replace("rc1pass", a.renderer), wkey, kname, sha)
         roof = {"bound": "l2" if shaded else "hbm", "achieved": round(achieved, 1), "peak": peak,
                 "unit": "GB/s", "frac": round(achieved / peak, 4),
@@ -1052,6 +1093,7 @@ def main():
             roof.update({"shaded_samples": shade[0], "shadow_chains": shade[1],
                          "sat_fetches": fetches,
                          "sat_fetches_per_shaded": round(fetches / max(1, shade[0]), 1)})
+    if rank == 0:
         metric = ("Msamples/s (rays x steps), Dir. Occlusion Shading (cone AO + cone shadows), "
                   f"{n}^3 volume at {W}^2" if dos else
                   "Msamples/s (rays x steps), Extinction-Based Shading (SAT AO + SAT shadows), "
@@ -1071,7 +1113,8 @@ def main():
             # fps and ms_per_step are throughput: frames overlap on the device (one
             # static view, split.nstreams launches of frames_per_launch frames in
             # flight); a frame is delivered when its launch ends, so its latency is
-            # about roofline.kernel_ms (its launch, with the other launches in flight)
+            # about roofline.kernel_ms (its launch, with the other launches in flight;
+            # measured by the kernel-time pass of --full)
             "frame_latency_ms_approx": None,
             "higher_is_better": True,
             "scaling": "strong",   # one fixed frame split over the GPUs
@@ -1115,9 +1158,10 @@ def main():
                                    else "per-wave batches") if shaded else None,
                        "empty_space_skip": f"macro cells 2^{macro}, auto (on at >= 15 % empty)"
                                            if macro > 0 else "off"},
-            "roofline": roof,
         }
-        res["frame_latency_ms_approx"] = round(kern_ms, 4)
+        if a.full:
+            res["roofline"] = roof
+            res["frame_latency_ms_approx"] = round(kern_ms, 4)
         if world > 1:
             coded = a.transport == "rccl" and a.exchange_code and a.format == "rgba16f"
             res["config"]["gather"] = ((f"{a.transport}: per-tile code of each rank's {a.format} tiles "
@@ -1135,7 +1179,7 @@ def main():
         if ebs:
             cells = (n + 2) ** 3
             sat_gpu_ms = N.lib().cvr_get_option(r.device.handle, b"sat_build_us") / 1e3
-            res["precompute"] = {"sat_ms": round(sat_ms, 2), "sat_cells": cells,
+            res["precompute"] = {"sat_ms": round(sat_ms, 2) if a.full else None, "sat_cells": cells,
                                  "sat_gpu_ms": round(sat_gpu_ms, 2),
                                  "sat_Mcells_s": round(cells / (sat_gpu_ms * 1e-3) / 1e6, 1),
                                  "what": "GenerateExtinctionSAT3DTex + BuildSAT on the GPU "
@@ -1145,9 +1189,10 @@ def main():
                                          "of the build + cell4 expansion kernels"}
         if a.postpass and world == 1:
             res["postpass"] = postpass_bench(r, dev, W, H, a.steps)
-        if world == 1 and a.renderer == "rc1pass" and not a.orbit and not a.no_cadence:
+        if (a.full and world == 1 and a.renderer == "rc1pass" and not a.orbit
+                and not a.no_cadence):
             res["plugin_cadence"] = cadence_lines(r, dev, W, H, fmt, cam, S_cam[0])
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             dos_cfg = None
             if dos:
                 dos_cfg = {"tf_rgba": tf_rgba, "res": r.ext_res,

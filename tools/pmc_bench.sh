@@ -6,7 +6,8 @@
 #   tools/pmc_bench.sh NAME KERNEL "BENCH ARGS" ["GROUP;GROUP;..."]
 #   e.g. tools/pmc_bench.sh ebs shaded_march_kernel "--renderer ebs"
 #
-# Output: gpurun_out/pmc_NAME/{gN/,gN.log,summary.json}.  A crash, abort or
+# Output: $RUN_DIR/pmc_NAME/{gN/,gN.log,summary.json} (RUN_DIR: out/ by default).
+# bench.py runs plain here (without --full).  A crash, abort or
 # time limit ends the script (no retry); a rejected counter group is reported.
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
@@ -14,7 +15,7 @@ export TMPDIR=/tmp
 NAME=$1; KERNEL=$2; ARGS=$3
 GROUPS_DEFAULT="FETCH_SIZE;WRITE_SIZE;TCC_HIT_sum TCC_MISS_sum;SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_INST_ANY;TD_TD_BUSY TD_TC_STALL TA_TA_BUSY TA_ADDR_STALLED_BY_TC_CYCLES;TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum;SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVES;GRBM_GUI_ACTIVE GRBM_COUNT"
 GRP_LIST=${4:-$GROUPS_DEFAULT}
-OUT=gpurun_out/pmc_$NAME
+OUT=${RUN_DIR:-out}/pmc_$NAME
 rm -rf "$OUT"; mkdir -p "$OUT"
 IFS=';' read -ra GRPS <<< "$GRP_LIST"
 i=0
