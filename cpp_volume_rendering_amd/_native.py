@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = (
     "cvr_tf1d_build_rgbt", "cvr_read_tf1d", "cvr_read_raw", "cvr_read_syn", "cvr_read_pvm",
     "cvr_read_camera_state", "cvr_read_light_position", "cvr_read_light", "cvr_build_cone_tables",
     "cvr_set_extinction_volume", "cvr_copy_extinction_level", "cvr_render_dosct",
+    "cvr_compute_light_cache_dosct", "cvr_set_light_cache", "cvr_copy_light_cache",
+    "cvr_render_preillum", "cvr_render_dosct_preillum",
     "cvr_tf1d_ext_lut", "cvr_set_extinction_sat", "cvr_copy_extinction_sat", "cvr_sat_layout_check", "cvr_render_extbsd",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
@@ -219,6 +221,13 @@ def lib() -> ctypes.CDLL:
         "cvr_copy_extinction_level": ([P, I, FP, IP, IP], I),
         "cvr_render_dosct": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DosParams),
                               ctypes.POINTER(Output)], I),
+        "cvr_compute_light_cache_dosct": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DosParams), IP], I),
+        "cvr_set_light_cache": ([P, P, IP], I),
+        "cvr_copy_light_cache": ([P, P, ctypes.c_size_t, IP], I),
+        "cvr_render_preillum": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DosParams),
+                                 ctypes.POINTER(Output)], I),
+        "cvr_render_dosct_preillum": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DosParams), IP,
+                                       ctypes.POINTER(Output)], I),
         "cvr_tf1d_ext_lut": ([DP, I, DP, I, I, I, I, FP], I),
         "cvr_set_extinction_sat": ([P, FP, I], I),
         "cvr_copy_extinction_sat": ([P, FP, ctypes.c_size_t, IP], I),

@@ -44,6 +44,19 @@ void free_dev(void*& p) {
   p = nullptr;
 }
 
+// The pre-illumination light cache goes with the state it was computed from: a
+// new volume, TF or extinction pyramid drops it (after the device has drained).
+void light_cache_drop(Ctx* c) {
+  void* p = c->d_lcache;
+  free_dev(p);
+  c->d_lcache = nullptr;
+  c->lc_bytes = 0;
+  c->lc_dims[0] = c->lc_dims[1] = c->lc_dims[2] = 0;
+  c->lc_key.valid = 0;
+  c->lc_readers = 0;
+  c->lc_written = false;
+}
+
 // Before a state change writes or frees device state that frames read (volume
 // cells, TF, gradient, occupancy, cone tables, extinction pyramid, SAT): frames
 // may be in flight on any render stream the caller rotates (non-blocking
@@ -271,6 +284,8 @@ void cvr_destroy(cvr_ctx* ctx) {
   for (auto& J : c->flat) cvr::flat_release(J);
   p = c->d_cones; free_dev(p); c->d_cones = nullptr;
   delete[] c->cone_tab;
+  light_cache_drop(c);
+  if (c->lc_ev) (void)hipEventDestroy(c->lc_ev);
   p = c->d_total; free_dev(p); c->d_total = nullptr;
   free_dev(c->d_scratch);
   if (c->side) (void)hipStreamSynchronize(c->side);
@@ -568,6 +583,7 @@ int cvr_get_option(const cvr_ctx* ctx, const char* key) {
       if (J.owned && J.stream == c->stream) return (int)(J.cap / 1000);
     return 0;
   }
+  if (!std::strcmp(key, "light_cache_builds")) return c->lc_builds;   // read-only
   if (!std::strcmp(key, "sat_chunk")) return c->sat_chunk;
   if (!std::strcmp(key, "sat_layout")) return c->sat_layout;
   if (!std::strcmp(key, "sat_keep_scratch")) return c->sat_keep_scratch;
@@ -599,7 +615,8 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
       b += cvr_device_bytes(cvr_group_member(const_cast<cvr_ctx*>(ctx), i));
     return b;
   }
-  return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes;
+  return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
+         c->lc_bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {
@@ -657,6 +674,7 @@ static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, in
   { void* p = c->d_sat_scratch; free_dev(p); c->d_sat_scratch = nullptr; }
   c->sat_dims[0] = c->sat_dims[1] = c->sat_dims[2] = 0;
   c->cone_valid = 0;
+  light_cache_drop(c);
   HIP_TRY(c, hipMalloc((void**)&c->d_lut, nv * sizeof(uint16_t)));
   uint16_t* d_lut = c->d_lut;
   hipError_t e = hipMemcpyAsync(d_lut, lut.data(), nv * sizeof(uint16_t), hipMemcpyHostToDevice,
@@ -704,6 +722,7 @@ cvr_status cvr_set_transfer_function(cvr_ctx* ctx, const float* rgbt, int n) {
     if (i % 4 == 3) amax = std::isfinite(q[i]) ? std::max(amax, q[i]) : NAN;
   }
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
+  light_cache_drop(c);
   if (n != c->tf_n) {
     void* p = c->d_tf; free_dev(p); c->d_tf = nullptr;
     HIP_TRY(c, hipMalloc((void**)&c->d_tf, (size_t)n * 16));
@@ -1530,6 +1549,7 @@ cvr_status cvr_set_extinction_volume(cvr_ctx* ctx, const float* tf_rgba, int n, 
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
   { void* p = c->d_ext; free_dev(p); c->d_ext = nullptr; c->ext_levels = 0; }
   { void* p = c->d_ext_cells; free_dev(p); c->d_ext_cells = nullptr; }
+  light_cache_drop(c);
   // cell8 texels are addressed with 32-bit byte offsets (16 B each)
   if (off[nl] > (1LL << 28)) return fail(c, CVR_ERR_ARG, "cvr_set_extinction_volume: resolution too large");
   float4* d_tf = nullptr;
@@ -1604,44 +1624,48 @@ static bool same_cone(const cvr_cone_params& a, const cvr_cone_params& b) {
   return std::memcmp(&a, &b, sizeof(a)) == 0;
 }
 
-cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
-                            const cvr_output* o) {
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (c && c->group)
-    return cvr::group_render(c, f, 1, o, [&](cvr_ctx* _m, const cvr_frame* mf, int, const cvr_output* mo) {
-      return cvr_render_dosct(_m, mf, p, mo);
-    });
-  if (!c) return CVR_ERR_ARG;
-  if (!f || !p || !o || !o->rgba) return fail(c, CVR_ERR_ARG, "cvr_render_dosct: null argument");
+// The cone parameters a frame traces with: covered distance <= 0 -> the volume
+// diagonal * 0.50 / 0.75 (GetDiagonal in double, dosrcrenderer.cpp:112-113)
+static void resolve_cone_params(const Ctx* c, const cvr_dos_params* p, cvr_cone_params cp[2]) {
+  cp[0] = p->occlusion;
+  cp[1] = p->shadow;
+  double vw = c->N[0] * (double)c->scale[0], vh = c->N[1] * (double)c->scale[1],
+         vd = c->N[2] * (double)c->scale[2];
+  const double diag = std::sqrt(vw * vw + vh * vh + vd * vd);
+  if (!(cp[0].covered_distance > 0.0f)) cp[0].covered_distance = (float)(diag * 0.50f);
+  if (!(cp[1].covered_distance > 0.0f)) cp[1].covered_distance = (float)(diag * 0.75f);
+}
 
-  if (o->format != CVR_FORMAT_RGBA32F && o->format != CVR_FORMAT_RGBA16F)
-    return fail(c, CVR_ERR_ARG, "cvr_render_dosct: unknown output format %d", o->format);
-  if (f->width < 1 || f->height < 1 || f->width > 32768 || f->height > 32768)
-    return fail(c, CVR_ERR_ARG, "cvr_render_dosct: bad viewport %dx%d", f->width, f->height);
-  if (!c->d_cells || !c->d_tf) return fail(c, CVR_ERR_STATE, "cvr_render_dosct: no volume or TF");
-  if (!c->d_ext) return fail(c, CVR_ERR_STATE, "cvr_render_dosct: needs cvr_set_extinction_volume");
-  const bool phong = p->apply_gradient_shading != 0;
-  if (phong && !c->d_grad) return fail(c, CVR_ERR_STATE, "cvr_render_dosct: Phong needs cvr_set_gradient");
-  if (p->shadow_type < 0 || p->shadow_type > 2) return fail(c, CVR_ERR_ARG, "cvr_render_dosct: bad shadow type");
-  if (f->nranks > 1 && (f->tile_size < 16 || f->tile_size % 16 != 0 || f->rank < 0 || f->rank >= f->nranks))
-    return fail(c, CVR_ERR_ARG, "cvr_render_dosct: bad tiling");
+// The DosArgs of a frame: the checks every DOS entry point shares, the cone tables
+// (rebuilt and uploaded when the cone parameters changed) and the shaders' uniforms.
+// o == null: no frame is rendered (cvr_compute_light_cache), so the output and
+// viewport checks and the gradient requirement do not apply.  need_cones: the
+// entry point traces cones (needs the extinction pyramid and the tables).
+static cvr_status dos_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_dos_params* p,
+                              const cvr_output* o, bool need_cones, cvr::DosArgs& Q, int& ntiles,
+                              size_t& npix, cvr_cone_params cp[2]) {
+  if (!f || !p || (o && !o->rgba)) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
+
+  if (o && o->format != CVR_FORMAT_RGBA32F && o->format != CVR_FORMAT_RGBA16F)
+    return fail(c, CVR_ERR_ARG, "%s: unknown output format %d", who, o->format);
+  if (o && (f->width < 1 || f->height < 1 || f->width > 32768 || f->height > 32768))
+    return fail(c, CVR_ERR_ARG, "%s: bad viewport %dx%d", who, f->width, f->height);
+  if (!c->d_cells || !c->d_tf) return fail(c, CVR_ERR_STATE, "%s: no volume or TF", who);
+  if (need_cones && !c->d_ext) return fail(c, CVR_ERR_STATE, "%s: needs cvr_set_extinction_volume", who);
+  const bool phong = o && p->apply_gradient_shading != 0;
+  if (phong && !c->d_grad) return fail(c, CVR_ERR_STATE, "%s: Phong needs cvr_set_gradient", who);
+  if (p->shadow_type < 0 || p->shadow_type > 2) return fail(c, CVR_ERR_ARG, "%s: bad shadow type", who);
+  if (o && f->nranks > 1 && (f->tile_size < 16 || f->tile_size % 16 != 0 || f->rank < 0 || f->rank >= f->nranks))
+    return fail(c, CVR_ERR_ARG, "%s: bad tiling", who);
   HIP_TRY(c, hipSetDevice(c->device));
 
-  // cone tables: covered distance <= 0 -> the volume diagonal * 0.50 / 0.75
-  // (GetDiagonal in double, dosrcrenderer.cpp:112-113)
-  cvr_cone_params cp[2] = {p->occlusion, p->shadow};
-  {
-    double vw = c->N[0] * (double)c->scale[0], vh = c->N[1] * (double)c->scale[1],
-           vd = c->N[2] * (double)c->scale[2];
-    const double diag = std::sqrt(vw * vw + vh * vh + vd * vd);
-    if (!(cp[0].covered_distance > 0.0f)) cp[0].covered_distance = (float)(diag * 0.50f);
-    if (!(cp[1].covered_distance > 0.0f)) cp[1].covered_distance = (float)(diag * 0.75f);
-  }
-  if (!c->cone_valid || !same_cone(cp[0], c->cone_key[0]) || !same_cone(cp[1], c->cone_key[1])) {
+  resolve_cone_params(c, p, cp);
+  if (need_cones &&
+      (!c->cone_valid || !same_cone(cp[0], c->cone_key[0]) || !same_cone(cp[1], c->cone_key[1]))) {
     if (!c->cone_tab) c->cone_tab = new cvr_cone_tables[2];
     for (int k = 0; k < 2; k++) {
       cvr_status st = cvr_build_cone_tables(&cp[k], c->ext_sigma0, &c->cone_tab[k]);
-      if (st != CVR_OK) return fail(c, st, "cvr_render_dosct: cone tables (%s)", k ? "shadow" : "occlusion");
+      if (st != CVR_OK) return fail(c, st, "%s: cone tables (%s)", who, k ? "shadow" : "occlusion");
     }
     std::vector<float> up(2 * CVR_MAX_CONE_SECTIONS * 4, 0.0f);
     for (int k = 0; k < 2; k++)
@@ -1656,12 +1680,10 @@ cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_para
     c->cone_valid = 1;
   }
 
-  cvr::DosArgs Q{};
-  int ntiles = 0;
-  size_t npix = 0;
+  Q = cvr::DosArgs{};
   fill_frame_args(c, f, p->step, Q.a, ntiles, npix);
   Q.a.filter_bits = c->filter_bits;   // GL_LINEAR weights of every fetch (CVR-SPEC-8 at 8)
-  if (c->cell_skip > 0) {   // the per-cell skip flags in the count / emit march
+  if (o && c->cell_skip > 0) {   // the per-cell skip flags in the count / emit march
     const cvr_status st = cell_flags_or_off(c);
     if (st == CVR_OK) {
       Q.a.cell_skip = 1;
@@ -1670,7 +1692,7 @@ cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_para
       return st;
     }
   }
-  Q.a.out_half = o->format == CVR_FORMAT_RGBA16F;
+  Q.a.out_half = o && o->format == CVR_FORMAT_RGBA16F;
   Q.a.ka = p->ka;   // Phong ambient/diffuse/specular weights of the surface term
   Q.a.kd = p->kd;
   Q.a.ks = p->ks;
@@ -1696,7 +1718,7 @@ cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_para
   Q.spot_cos = std::cos(3.14159265358979323846f * p->light.spot_angle_deg / 180.0f);
   Q.zero_skip = c->ext_finite;
   Q.count_taps = c->shade_counters ? 1 : 0;
-  for (int k = 0; k < 2; k++) {
+  for (int k = 0; need_cones && k < 2; k++) {
     cvr::DosCone& C = k ? Q.sdw : Q.occ;
     const cvr_cone_tables& T = c->cone_tab[k];
     for (int i = 0; i < 3; i++) C.counts[i] = T.counts[i];
@@ -1736,10 +1758,253 @@ cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_para
     }
   }
 
+  return CVR_OK;
+}
+
+cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
+                            const cvr_output* o) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (c && c->group)
+    return cvr::group_render(c, f, 1, o, [&](cvr_ctx* _m, const cvr_frame* mf, int, const cvr_output* mo) {
+      return cvr_render_dosct(_m, mf, p, mo);
+    });
+  if (!c) return CVR_ERR_ARG;
+  if (!o) return fail(c, CVR_ERR_ARG, "cvr_render_dosct: null argument");
+  cvr::DosArgs Q;
+  int ntiles = 0;
+  size_t npix = 0;
+  cvr_cone_params cp[2];
+  const cvr_status st = dos_prepare(c, "cvr_render_dosct", f, p, o, true, Q, ntiles, npix, cp);
+  if (st != CVR_OK) return st;
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t st) {
     return cvr::launch_dos(*c, Q, out, smp, shade, ts, st);
   }, c->shade_flat != 0);
+}
+
+// ---------------------------------------------------------------------------
+// Pre-illumination of the DOS renderer (PreIlluminationStructuredVolume): the
+// light cache and the march over it (lightcache.hip)
+// ---------------------------------------------------------------------------
+
+// The multi-device split of this path is not built: a group context refuses it.
+#define NO_GROUP(c, who)                                                                       \
+  do {                                                                                         \
+    if ((c)->group)                                                                            \
+      return fail(c, CVR_ERR_STATE, who ": not available on a group context (cvr_create_group)"); \
+  } while (0)
+
+static bool light_cache_dims_ok(const int dims[3]) {
+  if (!dims) return false;
+  for (int i = 0; i < 3; i++)
+    if (dims[i] < 2 || dims[i] > cvr::kMaxLightCacheDim) return false;
+  return true;
+}
+
+// Before the cache is written (or freed) on the context stream: frames that read
+// it on this stream are ordered before the write; frames on other streams, or an
+// earlier write on another stream, are not, so the device drains first.
+static cvr_status light_cache_write_begin(Ctx* c) {
+  const bool foreign_reader = c->lc_readers == 2 || (c->lc_readers == 1 && c->lc_reader != c->stream);
+  const bool foreign_writer = c->lc_written && c->lc_writer != c->stream;
+  if (foreign_reader || foreign_writer) QUIESCE(c);
+  c->lc_readers = 0;
+  c->lc_written = false;
+  return CVR_OK;
+}
+
+// The cache buffer for `dims` (kept when the size is unchanged).
+static cvr_status light_cache_reserve(Ctx* c, const int dims[3]) {
+  const size_t bytes = (size_t)dims[0] * dims[1] * dims[2] * 4;
+  if (!c->d_lcache || bytes != c->lc_bytes) {
+    QUIESCE(c);   // frames in flight on any stream may read the buffer freed below
+    light_cache_drop(c);
+    HIP_TRY(c, hipMalloc((void**)&c->d_lcache, bytes));
+    c->lc_bytes = bytes;
+  }
+  for (int i = 0; i < 3; i++) c->lc_dims[i] = dims[i];
+  return CVR_OK;
+}
+
+// EyeCamUp: the cup of Camera::GetCameraVectors (camera.cpp:336-341), glm float
+// arithmetic; with use_view the view matrix's own up row (the same vector of a
+// lookAt matrix, which keeps its centre private)
+static void eye_cam_up(const cvr_frame* f, float out[3]) {
+  if (f->use_view) {
+    out[0] = f->view[1]; out[1] = f->view[5]; out[2] = f->view[9];
+    return;
+  }
+  const V3 eye{f->camera.eye[0], f->camera.eye[1], f->camera.eye[2]};
+  const V3 center{f->camera.center[0], f->camera.center[1], f->camera.center[2]};
+  const V3 up{f->camera.up[0], f->camera.up[1], f->camera.up[2]};
+  const V3 dir = gnormalize(sub(center, eye));
+  const V3 fwd{-dir.x, -dir.y, -dir.z};
+  const V3 right = gnormalize(cross(up, fwd));
+  const V3 cup = gnormalize(cross(fwd, right));
+  out[0] = cup.x; out[1] = cup.y; out[2] = cup.z;
+}
+
+static void light_cache_key(const Ctx* c, const cvr_frame* f, const cvr_dos_params* p,
+                            const cvr_cone_params cp[2], const int dims[3], Ctx::LightCacheKey& k) {
+  k = Ctx::LightCacheKey{};
+  k.valid = 1;
+  for (int i = 0; i < 3; i++) k.dims[i] = dims[i];
+  k.apply_occlusion = p->apply_occlusion != 0;
+  k.apply_shadow = p->apply_shadow != 0;
+  k.shadow_type = p->shadow_type;
+  k.filter_bits = c->filter_bits;
+  // a cone or a light that is switched off does not reach the cache
+  if (k.apply_occlusion) k.cone[0] = cp[0];
+  if (k.apply_shadow) {
+    k.cone[1] = cp[1];
+    k.light = p->light;
+  }
+  if (k.apply_occlusion) {
+    for (int i = 0; i < 3; i++) k.eye[i] = f->camera.eye[i];
+    eye_cam_up(f, k.cam_up);
+  }
+}
+
+// PreComputeLightCache (dosrcrenderer.cpp:555-655), queued on the context stream.
+static cvr_status light_cache_compute(Ctx* c, const char* who, const cvr_frame* f,
+                                      const cvr_dos_params* p, const int dims[3]) {
+  if (!light_cache_dims_ok(dims))
+    return fail(c, CVR_ERR_ARG, "%s: light cache dimensions must be in [2, %d]", who, cvr::kMaxLightCacheDim);
+  cvr::DosArgs Q;
+  int ntiles = 0;
+  size_t npix = 0;
+  cvr_cone_params cp[2];
+  cvr_status st = dos_prepare(c, who, f, p, nullptr, true, Q, ntiles, npix, cp);
+  if (st != CVR_OK) return st;
+  if (c->native_exp)
+    return fail(c, CVR_ERR_ARG, "%s: the light cache has no native_exp (tolerance) form", who);
+  if ((st = light_cache_write_begin(c)) != CVR_OK) return st;
+  if ((st = light_cache_reserve(c, dims)) != CVR_OK) return st;
+  cvr::LightCacheArgs P{};
+  for (int i = 0; i < 3; i++) {
+    P.dims[i] = dims[i];
+    // VolumeScales * (VolumeDimensions / LightCacheDimensions), float (:537)
+    P.vs[i] = c->scale[i] * ((float)c->N[i] / (float)dims[i]);
+  }
+  eye_cam_up(f, P.cam_up);
+  c->lc_key.valid = 0;
+  HIP_TRY(c, cvr::launch_light_cache(Q, P, c->d_ext_cells, c->d_lcache, c->stream));
+  if (!c->lc_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lc_ev, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->lc_ev, c->stream));
+  c->lc_written = true;
+  c->lc_writer = c->stream;
+  c->lc_builds++;
+  light_cache_key(c, f, p, cp, dims, c->lc_key);
+  return CVR_OK;
+}
+
+cvr_status cvr_compute_light_cache_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
+                                         const int dims[3]) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_compute_light_cache_dosct");
+  return light_cache_compute(c, "cvr_compute_light_cache_dosct", f, p, dims);
+}
+
+cvr_status cvr_set_light_cache(cvr_ctx* ctx, const uint16_t* rg_half, const int dims[3]) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_set_light_cache");
+  if (!rg_half) return fail(c, CVR_ERR_ARG, "cvr_set_light_cache: null argument");
+  if (!light_cache_dims_ok(dims))
+    return fail(c, CVR_ERR_ARG, "cvr_set_light_cache: light cache dimensions must be in [2, %d]",
+                cvr::kMaxLightCacheDim);
+  QUIESCE(c);   // frames in flight on any stream read the cache replaced below
+  c->lc_readers = 0;
+  c->lc_written = false;
+  const cvr_status st = light_cache_reserve(c, dims);
+  if (st != CVR_OK) return st;
+  c->lc_key.valid = 0;   // not this library's compute: cvr_render_dosct_preillum recomputes
+  HIP_TRY(c, hipMemcpy(c->d_lcache, rg_half, c->lc_bytes, hipMemcpyHostToDevice));
+  return CVR_OK;
+}
+
+cvr_status cvr_copy_light_cache(cvr_ctx* ctx, uint16_t* out, size_t capacity, int dims[3]) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_copy_light_cache");
+  if (!c->d_lcache) return fail(c, CVR_ERR_STATE, "cvr_copy_light_cache: no light cache");
+  if (dims)
+    for (int i = 0; i < 3; i++) dims[i] = c->lc_dims[i];
+  if (!out) return CVR_OK;
+  if (capacity < c->lc_bytes / 2)
+    return fail(c, CVR_ERR_ARG, "cvr_copy_light_cache: need %zu halfs", c->lc_bytes / 2);
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->lc_written && c->lc_writer != c->stream) HIP_TRY(c, hipEventSynchronize(c->lc_ev));
+  HIP_TRY(c, hipMemcpy(out, c->d_lcache, c->lc_bytes, hipMemcpyDeviceToHost));
+  return CVR_OK;
+}
+
+cvr_status cvr_render_preillum(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
+                               const cvr_output* o) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_render_preillum");
+  if (!o) return fail(c, CVR_ERR_ARG, "cvr_render_preillum: null argument");
+  cvr::DosArgs Q;
+  int ntiles = 0;
+  size_t npix = 0;
+  cvr_cone_params cp[2];
+  const cvr_status st = dos_prepare(c, "cvr_render_preillum", f, p, o, false, Q, ntiles, npix, cp);
+  if (st != CVR_OK) return st;
+  if (!c->d_lcache)
+    return fail(c, CVR_ERR_STATE, "cvr_render_preillum: no light cache (cvr_compute_light_cache_dosct / "
+                                  "cvr_set_light_cache)");
+  cvr::LightCacheView V{};
+  V.rg = c->d_lcache;
+  for (int i = 0; i < 3; i++) {
+    V.d[i] = c->lc_dims[i];
+    V.s[i] = (float)c->lc_dims[i] / Q.G[i];   // L / G, rounded once
+    V.m[i] = (float)(c->lc_dims[i] - 1);
+  }
+  // a cache written on another stream: this frame waits for that write
+  if (c->lc_written && c->lc_writer != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->lc_ev, 0));
+  if (c->lc_readers == 0) {
+    c->lc_readers = 1;
+    c->lc_reader = c->stream;
+  } else if (c->lc_reader != c->stream) {
+    c->lc_readers = 2;
+  }
+  return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
+                                                unsigned long long* ts, hipStream_t st) {
+    return cvr::launch_preillum(*c, Q, V, out, smp, shade, ts, st);
+  }, c->shade_flat != 0);
+}
+
+// RC1PConeTracingDirOcclusionShading::Update with pre-illumination on
+// (dosrcrenderer.cpp:134-143): PreComputeLightCache, then the cached march.  The
+// reference recomputes on every Update; here the compute is skipped while nothing
+// the cache depends on has changed.
+cvr_status cvr_render_dosct_preillum(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
+                                     const int dims[3], const cvr_output* o) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_render_dosct_preillum");
+  if (!f || !p || !o || !o->rgba) return fail(c, CVR_ERR_ARG, "cvr_render_dosct_preillum: null argument");
+  if (!light_cache_dims_ok(dims))
+    return fail(c, CVR_ERR_ARG, "cvr_render_dosct_preillum: light cache dimensions must be in [2, %d]",
+                cvr::kMaxLightCacheDim);
+  if (p->shadow_type < 0 || p->shadow_type > 2)
+    return fail(c, CVR_ERR_ARG, "cvr_render_dosct_preillum: bad shadow type");
+  bool fresh = c->d_lcache && c->lc_key.valid;
+  if (fresh) {
+    cvr_cone_params cp[2];
+    resolve_cone_params(c, p, cp);
+    Ctx::LightCacheKey k;
+    light_cache_key(c, f, p, cp, dims, k);
+    fresh = std::memcmp(&k, &c->lc_key, sizeof(k)) == 0;
+  }
+  if (!fresh) {
+    const cvr_status st = light_cache_compute(c, "cvr_render_dosct_preillum", f, p, dims);
+    if (st != CVR_OK) return st;
+  }
+  return cvr_render_preillum(ctx, f, p, o);
 }
 
 

@@ -136,6 +136,24 @@ struct DosArgs {
   DosCone occ, sdw;
 };
 
+// Pre-illumination (lightcache.hip): the light cache is an RG16F 3D image, one
+// uint32 per voxel (Idao in the low half, Idcs in the high half), x-fastest.
+// Its producer is the DOS cone kernel today; any producer that fills the same
+// image (cvr_set_light_cache) feeds the same march.
+constexpr int kMaxLightCacheDim = 512;
+struct LightCacheArgs {              // the computation's own uniforms (DosArgs holds the rest)
+  int dims[3];                       // LightCacheDimensions
+  int nb[3];                         // 4x4x4 voxel blocks per axis (set by the launcher)
+  float vs[3];                       // VolumeScales * (VolumeDimensions / LightCacheDimensions)
+  float cam_up[3];                   // EyeCamUp (Camera::GetCameraVectors' cup)
+};
+struct LightCacheView {              // what the cached march's fetch reads
+  const uint32_t* rg;
+  int d[3];
+  float s[3];                        // L / G: texel coordinate = fma(p, L / G, -0.5)
+  float m[3];                        // L - 1 (clamp-to-edge bound)
+};
+
 // Extinction-based shading (ebs.hip): the SAT and the shader's uniforms.
 struct EbsArgs {
   Rc1passArgs a;                     // ray, volume, TF, Blinn-Phong constants, tiles
@@ -367,6 +385,30 @@ struct Ctx {
   cvr_cone_params cone_key[2] = {};
   int cone_valid = 0;
   cvr_cone_tables* cone_tab = nullptr;   // host copies [2]
+  // pre-illumination light cache (lightcache.hip): RG16F, 4 B per voxel
+  uint32_t* d_lcache = nullptr;
+  int lc_dims[3] = {0, 0, 0};
+  size_t lc_bytes = 0;
+  int lc_builds = 0;                 // computes so far (option "light_cache_builds", read-only)
+  // what the cache was computed from (cvr_render_dosct_preillum skips the compute
+  // when nothing of it changed); invalid after cvr_set_light_cache
+  struct LightCacheKey {
+    int valid = 0;
+    int dims[3] = {0, 0, 0};
+    int apply_occlusion = 0, apply_shadow = 0, shadow_type = 0, filter_bits = 0;
+    cvr_cone_params cone[2] = {};
+    cvr_light light = {};
+    float eye[3] = {0, 0, 0}, cam_up[3] = {0, 0, 0};   // compared only with occlusion on
+  } lc_key;
+  // frames that read the cache since it was last written: on one stream (a later
+  // write on that stream is ordered behind them) or on several (the write drains
+  // the device first)
+  hipStream_t lc_reader = nullptr;
+  int lc_readers = 0;                // 0 none, 1 lc_reader only, 2 several streams
+  // the last compute: its stream and end event (a frame on another stream waits for it)
+  hipEvent_t lc_ev = nullptr;
+  hipStream_t lc_writer = nullptr;
+  bool lc_written = false;
   unsigned long long* d_tile_samples = nullptr;   // per-wave-tile sample counts (zeroed)
   int tile_samples_n = 0;
   // d_tile_samples and d_shade are one set per context: a frame that uses them on
@@ -452,6 +494,12 @@ hipError_t launch_ebs(const Ctx& c, const EbsArgs& q, float4* out, uint32_t* sam
 hipError_t launch_dos(const Ctx& c, const DosArgs& q, float4* out, uint32_t* samples,
                       unsigned long long* shade,
                       unsigned long long* tile_samples, hipStream_t s);
+// lightcache.hip: the light cache of the DOS cones, and the march that reads a cache
+hipError_t launch_light_cache(const DosArgs& q, const LightCacheArgs& p, const uint4* ext,
+                              uint32_t* out, hipStream_t s);
+hipError_t launch_preillum(const Ctx& c, const DosArgs& q, const LightCacheView& v, float4* out,
+                           uint32_t* samples, unsigned long long* shade,
+                           unsigned long long* tile_samples, hipStream_t s);
 // iso.hip: raw per-block extremes (uint2), and the isosurface march (variant 0/1)
 hipError_t launch_block_minmax(const void* vox, int bpv, const int N[3], const int nb[3], uint2* out,
                                hipStream_t s);

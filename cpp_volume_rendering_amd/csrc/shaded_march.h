@@ -23,11 +23,17 @@
 // direction, g: the gradient sample when Phong shading is on, else null; lit
 // and fetches count the shadow traces and the secondary texture fetches, for the
 // roofline).
+// A shader may also have
+//   static bool gate(const Args&);
+// the march then composites a sample only `if (src.a > 0 && gate(Q))`
+// (obj_ray_marching.comp:294, 312: `Shade`); without it every sample with
+// alpha > 0 is composited.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "cvr_device.h"
 #include "cvr_internal.h"
@@ -44,6 +50,15 @@ __device__ __forceinline__ f3 vmad(f3 d, float t, f3 p) {
 __device__ __forceinline__ f3 cross3(f3 x, f3 y) {   // glm / GLSL cross, no fma
   return f3{x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y};
 }
+
+template <class SH, class = void>
+struct ShaderGate {
+  __device__ static __forceinline__ bool on(const typename SH::Args&) { return true; }
+};
+template <class SH>
+struct ShaderGate<SH, std::void_t<decltype(&SH::gate)>> {
+  __device__ static __forceinline__ bool on(const typename SH::Args& Q) { return SH::gate(Q); }
+};
 
 #ifndef CVR_SHADED_COLGROUP
 #define CVR_SHADED_COLGROUP 4
@@ -95,6 +110,7 @@ shaded_march_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
   const float step = A.step, fn = (float)A.tf_n;
   float s = 0.0f;
   const bool wave_in_box = __ballot(active && r.outside) == 0;   // else clamp positions
+  const bool gate = ShaderGate<SH>::on(Q);
 
   for (;;) {
     // ---- march until the wave holds a full batch of jobs --------------------
@@ -113,7 +129,7 @@ shaded_march_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
         if (SH::kFB) quantise_weights<SH::kFB>(sp);   // filter_bits: volume and gradient weights
         const float4 sc = classify<SH::kFB>(tfp, fn, trilerp_cell(cells[sp.idx], sp.ax, sp.ay, sp.az));
         cnt++;
-        if (sc.w > 0.0f) {
+        if (sc.w > 0.0f && gate) {
           const int slot = lane * kJobsPerLane + n;
           const f3 tx = vmad(r.dir, tt, r.tpos);        // tx_pos, box at [0, G]
           jpx[slot] = tx.x; jpy[slot] = tx.y; jpz[slot] = tx.z;
@@ -260,6 +276,7 @@ shaded_jobs_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
   uint32_t cnt = 0, rounds = 0, tjobs = 0;   // rounds, tjobs: wave-uniform
   bool any_job = false;
   const bool skip = A.cell_skip > 0;   // per-cell skip flags (march_common.h cell_empty)
+  const bool gate = ShaderGate<SH>::on(Q);
   for (;;) {   // one sample per live lane per round (wave-uniform loop)
     if (__ballot(active) == 0) break;
     bool pushed = false;
@@ -286,7 +303,7 @@ shaded_jobs_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
         sc = classify<SH::kFB>(tfp, fn, trilerp_cell(raw, sp.ax, sp.ay, sp.az));
       }
       cnt++;
-      if (sc.w > 0.0f) {
+      if (sc.w > 0.0f && gate) {
         const float a = 1.0f - cvr_expf(-(sc.w * h));
         if (EMIT) {
           const f3 tx = vmad(r.dir, tt, r.tpos);        // tx_pos, box at [0, G]

@@ -333,6 +333,35 @@ class Device:
             out.append(a)
         return out
 
+    def compute_light_cache(self, frame: N.Frame, params: N.DosParams, dims=(32, 32, 32)):
+        """PreComputeLightCache (dosrcrenderer.cpp:555-655): the DOS cones of `params`
+        once per voxel of a dims cache, queued on the device's stream."""
+        d = (ctypes.c_int * 3)(*[int(v) for v in dims])
+        N.check(N.lib().cvr_compute_light_cache_dosct(self.handle, ctypes.byref(frame),
+                                                      ctypes.byref(params), d),
+                "cvr_compute_light_cache_dosct", self.handle)
+
+    def set_light_cache(self, rg_half: np.ndarray):
+        """Upload a (dz, dy, dx, 2) cache of binary16 (Idao, Idcs) pairs (float16, or
+        their uint16 bit patterns)."""
+        a = np.ascontiguousarray(rg_half)
+        if a.ndim != 4 or a.shape[3] != 2 or a.dtype.itemsize != 2:
+            raise ValueError("light cache must be (dz, dy, dx, 2) float16 / uint16")
+        d = (ctypes.c_int * 3)(a.shape[2], a.shape[1], a.shape[0])
+        N.check(N.lib().cvr_set_light_cache(self.handle, a.ctypes.data, d), "cvr_set_light_cache",
+                self.handle)
+
+    def light_cache(self) -> np.ndarray:
+        """The light cache as a (dz, dy, dx, 2) float16 array of (Idao, Idcs)."""
+        L = N.lib()
+        dims = (ctypes.c_int * 3)()
+        N.check(L.cvr_copy_light_cache(self.handle, None, 0, dims), "cvr_copy_light_cache",
+                self.handle)
+        a = np.zeros((dims[2], dims[1], dims[0], 2), np.float16)
+        N.check(L.cvr_copy_light_cache(self.handle, a.ctypes.data, a.size, dims),
+                "cvr_copy_light_cache", self.handle)
+        return a
+
     def device_bytes(self) -> int:
         return int(N.lib().cvr_device_bytes(self.handle))
 
@@ -619,8 +648,13 @@ class RC1PConeTracingDirOcclusionShading(RayCasting1Pass):
 
     POINT_LIGHT, SPOT_LIGHT, DIRECTIONAL_LIGHT = 0, 1, 2   # type_of_shadow combo (:543)
 
-    def __init__(self, device: int = 0, devices=None):
+    def __init__(self, device: int = 0, devices=None, pre_illumination: bool = False,
+                 light_cache_resolution=(32, 32, 32)):
         super().__init__(device, devices)
+        # "Use Pre-Illumination" (m_pre_illum_str_vol, dosrcrenderer.cpp:63-64, 134-143):
+        # the cones traced once per voxel of a light cache, one fetch per sample
+        self.pre_illumination = bool(pre_illumination)
+        self.light_cache_resolution = tuple(int(v) for v in light_cache_resolution)
         self.glsl_apply_occlusion = True            # dosrcrenderer.cpp:44
         self.glsl_apply_shadow = False              # :53
         self.type_of_shadow = self.POINT_LIGHT      # :59
@@ -671,6 +705,15 @@ class RC1PConeTracingDirOcclusionShading(RayCasting1Pass):
         return True
 
     _ENTRY = "cvr_render_dosct"
+
+    def render_to(self, frame: N.Frame, out: N.Output):
+        if not self.pre_illumination:
+            return super().render_to(frame, out)
+        dims = (ctypes.c_int * 3)(*[int(v) for v in self.light_cache_resolution])
+        N.check(N.lib().cvr_render_dosct_preillum(self.device.handle, ctypes.byref(frame),
+                                                  ctypes.byref(self._params), dims,
+                                                  ctypes.byref(out)),
+                "cvr_render_dosct_preillum", self.device.handle)
 
 
 class RC1PExtinctionBasedShading(RayCasting1Pass):

@@ -30,6 +30,9 @@
  *   cvr_render_dosct             <- RC1PConeTracingDirOcclusionShading::Update + Redraw
  *                                   cppvolrend/structured/rc1pdosct/dosrcrenderer.cpp:134-260
  *                                   (the dispatch of ray_bbox_marching.comp:658-734)
+ *   cvr_render_dosct_preillum    <- the same Update with "Use Pre-Illumination" on:
+ *                                   PreComputeLightCache (dosrcrenderer.cpp:555-655,
+ *                                   lightcachecomputation.comp) + obj_ray_marching.comp
  *   cvr_set_extinction_sat       <- RC1PExtinctionBasedShading::GenerateExtinctionSAT3DTex +
  *                                   SummedAreaTable3D<double>::BuildSAT
  *                                   cppvolrend/structured/rc1pextbsd/ebsrenderer.cpp:624-716,
@@ -57,7 +60,9 @@ extern "C" {
 /* Bumped whenever a public struct's layout or an entry point's meaning changes
  * (2: cvr_frame gained use_view/view).  Callers compare cvr_abi_version() with
  * the CVR_ABI_VERSION they were compiled against before the first call that
- * passes a struct. */
+ * passes a struct.  Entry points that are only added (the pre-illumination
+ * calls below) leave every existing caller valid and do not bump it; a caller
+ * that needs them looks them up by name. */
 #define CVR_ABI_VERSION 2
 
 typedef enum cvr_status {
@@ -422,6 +427,52 @@ cvr_status  cvr_copy_extinction_level(cvr_ctx* ctx, int level, float* out, int d
  * toward the light.  Needs cvr_set_extinction_volume. */
 cvr_status  cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* frame,
                              const cvr_dos_params* params, const cvr_output* out);
+
+/* ----------------------------------------------------------------------------
+ * Pre-illumination of the DOS renderer: the reference's "Use Pre-Illumination"
+ * switch (PreIlluminationStructuredVolume, cppvolrend/utils/preillumination.cpp;
+ * dosrcrenderer.cpp:63-64, 134-143, 555-655).  The occlusion and shadow cones are
+ * traced once per voxel of a small object-space grid, the LIGHT CACHE
+ * (rc1pdosct/lightcachecomputation.comp:523-547; 32^3 in the reference), stored
+ * as an RG16F image: per voxel two binary16 values (Idao, Idcs), x-fastest, 4
+ * bytes per voxel.  The march (_common_shaders/obj_ray_marching.comp:211-333)
+ * then shades each sample with ONE GL_LINEAR fetch of that image in place of two
+ * cone traces, and composites a sample only when occlusion or shadow is on.  An
+ * approximation, in the reference too: the image differs from cvr_render_dosct's
+ * (DESIGN.md §5b′ gives SSIM per cache resolution).  A new volume, transfer
+ * function or extinction pyramid drops the cache.  Group contexts
+ * (cvr_create_group) refuse these calls with CVR_ERR_STATE.
+ * -------------------------------------------------------------------------- */
+
+/* PreComputeLightCache: fills a cache of dims[3] voxels (each in [2, 512]) with
+ * the cones of `params` seen from frame->camera (the eye and its up vector reach
+ * the occlusion cones only), queued on the context stream.  Needs the volume, the
+ * TF and cvr_set_extinction_volume (else CVR_ERR_STATE).  Honours filter_bits;
+ * with option native_exp set it returns CVR_ERR_ARG (the cache has no tolerance
+ * form). */
+cvr_status  cvr_compute_light_cache_dosct(cvr_ctx* ctx, const cvr_frame* frame,
+                                          const cvr_dos_params* params, const int dims[3]);
+/* Upload a cache computed elsewhere (tests; a later producer such as the EBS
+ * light cache): 2 * dims[0] * dims[1] * dims[2] binary16 values. */
+cvr_status  cvr_set_light_cache(cvr_ctx* ctx, const uint16_t* rg_half, const int dims[3]);
+/* Copy the cache back after draining the context stream; capacity counts
+ * binary16 values.  out = NULL: dims only. */
+cvr_status  cvr_copy_light_cache(cvr_ctx* ctx, uint16_t* out, size_t capacity, int dims[3]);
+/* The cached march over whatever cache is set (CVR_ERR_STATE without one); of
+ * `params` it reads the step, the Blinn-Phong constants, the light position and
+ * the occlusion / shadow switches.  Outputs and counts as cvr_render_dosct. */
+cvr_status  cvr_render_preillum(cvr_ctx* ctx, const cvr_frame* frame,
+                                const cvr_dos_params* params, const cvr_output* out);
+/* RC1PConeTracingDirOcclusionShading::Update with the switch on: compute, then
+ * march.  The compute is skipped while nothing the cache depends on has changed
+ * since this context last computed it: the volume, the pyramid, dims, the
+ * switches, filter_bits, the parameters of a cone that is on, the light (shadow
+ * on), the eye and camera up (occlusion on).  A shadow-only cache therefore
+ * survives camera motion.  cvr_get_option(ctx, "light_cache_builds") counts the
+ * computes of a context. */
+cvr_status  cvr_render_dosct_preillum(cvr_ctx* ctx, const cvr_frame* frame,
+                                      const cvr_dos_params* params, const int dims[3],
+                                      const cvr_output* out);
 
 /* Extinction summed-area table of the current volume for the EBS renderer
  * (GenerateExtinctionSAT3DTex, ebsrenderer.cpp:624-716): a (W+2)(H+2)(D+2)

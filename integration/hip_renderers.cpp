@@ -80,6 +80,8 @@ HipDirOcclusionShading::HipDirOcclusionShading ()
   , type_of_shadow(0)
   , m_u_step_size(0.5f)
   , m_apply_gradient_shading(false)
+  , pre_illumination(false)                    // m_pre_illum_str_vol.SetActive(false) (:63)
+  , light_cache_resolution{32, 32, 32}         // SetLightCacheResolution(32, 32, 32) (:64)
   , m_params()
 {
   // ConeGaussianSampler settings of the constructor (:47-58); the covered
@@ -140,8 +142,27 @@ bool HipDirOcclusionShading::Update (vis::Camera* camera)
   return true;
 }
 
+void HipDirOcclusionShading::SetPreIllumination (bool active)
+{
+  pre_illumination = active;
+  SetOutdated();
+}
+
+void HipDirOcclusionShading::SetLightCacheResolution (int w, int h, int d)
+{
+  light_cache_resolution[0] = w;
+  light_cache_resolution[1] = h;
+  light_cache_resolution[2] = d;
+  SetOutdated();
+}
+
+// Update (:134-143): with the switch on, PreComputeLightCache and the march of
+// obj_ray_marching.comp; the library owns the cache (4 bytes per voxel) and
+// recomputes it only when something it depends on changed.
 cvr_status HipDirOcclusionShading::RenderFrame (const cvr_output* out)
 {
+  if (pre_illumination)
+    return cvr_render_dosct_preillum(m_cvr, &frame_, &m_params, light_cache_resolution, out);
   return cvr_render_dosct(m_cvr, &frame_, &m_params, out);
 }
 

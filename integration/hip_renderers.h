@@ -55,6 +55,17 @@ public:
   float m_u_step_size;
   bool m_apply_gradient_shading;
 
+  // m_pre_illum_str_vol (dosrcrenderer.h:69, PreIlluminationStructuredVolume): the
+  // "Use Pre-Illumination" switch and the light cache's resolution (32^3,
+  // dosrcrenderer.cpp:63-64).  The two setters are what the reference's
+  // SetImGuiComponents does on its checkbox and its "Update" button
+  // (preillumination.cpp:88-122, dosrcrenderer.cpp:330-336): they take the place of
+  // SetActive / SetLightCacheResolution + GenerateLightCacheTexture.
+  bool pre_illumination;
+  int light_cache_resolution[3];
+  void SetPreIllumination (bool active);
+  void SetLightCacheResolution (int w, int h, int d);
+
 protected:
   cvr_status RenderFrame (const cvr_output* out) override;
   cvr_dos_params m_params;
