@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "cvr_compute_light_cache_dosct", "cvr_set_light_cache", "cvr_copy_light_cache",
     "cvr_render_preillum", "cvr_render_dosct_preillum",
     "cvr_tf1d_ext_lut", "cvr_set_extinction_sat", "cvr_copy_extinction_sat", "cvr_sat_layout_check", "cvr_render_extbsd",
+    "cvr_compute_light_cache_extbsd", "cvr_render_extbsd_preillum",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
     "cvr_decode_tiles", "cvr_comm_init_local", "cvr_create_group", "cvr_group_size",
@@ -234,6 +235,9 @@ def lib() -> ctypes.CDLL:
         "cvr_sat_layout_check": ([IP, I, I, ctypes.POINTER(ctypes.c_ulonglong)], I),
         "cvr_render_extbsd": ([P, ctypes.POINTER(Frame), ctypes.POINTER(EbsParams),
                                ctypes.POINTER(Output)], I),
+        "cvr_compute_light_cache_extbsd": ([P, ctypes.POINTER(EbsParams), IP], I),
+        "cvr_render_extbsd_preillum": ([P, ctypes.POINTER(Frame), ctypes.POINTER(EbsParams), IP,
+                                        ctypes.POINTER(Output)], I),
         "cvr_iso_params_default": ([I, ctypes.POINTER(IsoParams)], None),
         "cvr_render_iso": ([P, ctypes.POINTER(Frame), ctypes.POINTER(IsoParams),
                             ctypes.POINTER(Output)], I),

@@ -45,7 +45,7 @@ void free_dev(void*& p) {
 }
 
 // The pre-illumination light cache goes with the state it was computed from: a
-// new volume, TF or extinction pyramid drops it (after the device has drained).
+// new volume, TF, extinction pyramid or SAT drops it (after the device has drained).
 void light_cache_drop(Ctx* c) {
   void* p = c->d_lcache;
   free_dev(p);
@@ -1919,7 +1919,7 @@ cvr_status cvr_set_light_cache(cvr_ctx* ctx, const uint16_t* rg_half, const int 
   c->lc_written = false;
   const cvr_status st = light_cache_reserve(c, dims);
   if (st != CVR_OK) return st;
-  c->lc_key.valid = 0;   // not this library's compute: cvr_render_dosct_preillum recomputes
+  c->lc_key.valid = 0;   // not this library's compute: cvr_render_*_preillum recompute
   HIP_TRY(c, hipMemcpy(c->d_lcache, rg_half, c->lc_bytes, hipMemcpyHostToDevice));
   return CVR_OK;
 }
@@ -1941,21 +1941,20 @@ cvr_status cvr_copy_light_cache(cvr_ctx* ctx, uint16_t* out, size_t capacity, in
   return CVR_OK;
 }
 
-cvr_status cvr_render_preillum(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
-                               const cvr_output* o) {
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
-  NO_GROUP(c, "cvr_render_preillum");
-  if (!o) return fail(c, CVR_ERR_ARG, "cvr_render_preillum: null argument");
+// The cached march over the context's cache (cvr_render_preillum, and the second
+// half of cvr_render_extbsd_preillum).
+static cvr_status preillum_march(Ctx* c, const char* who, const cvr_frame* f, const cvr_dos_params* p,
+                                 const cvr_output* o) {
+  if (!o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
   cvr::DosArgs Q;
   int ntiles = 0;
   size_t npix = 0;
   cvr_cone_params cp[2];
-  const cvr_status st = dos_prepare(c, "cvr_render_preillum", f, p, o, false, Q, ntiles, npix, cp);
+  const cvr_status st = dos_prepare(c, who, f, p, o, false, Q, ntiles, npix, cp);
   if (st != CVR_OK) return st;
   if (!c->d_lcache)
-    return fail(c, CVR_ERR_STATE, "cvr_render_preillum: no light cache (cvr_compute_light_cache_dosct / "
-                                  "cvr_set_light_cache)");
+    return fail(c, CVR_ERR_STATE, "%s: no light cache (cvr_compute_light_cache_dosct / "
+                                  "cvr_compute_light_cache_extbsd / cvr_set_light_cache)", who);
   cvr::LightCacheView V{};
   V.rg = c->d_lcache;
   for (int i = 0; i < 3; i++) {
@@ -1975,6 +1974,14 @@ cvr_status cvr_render_preillum(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_p
                                                 unsigned long long* ts, hipStream_t st) {
     return cvr::launch_preillum(*c, Q, V, out, smp, shade, ts, st);
   }, c->shade_flat != 0);
+}
+
+cvr_status cvr_render_preillum(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_params* p,
+                               const cvr_output* o) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_render_preillum");
+  return preillum_march(c, "cvr_render_preillum", f, p, o);
 }
 
 // RC1PConeTracingDirOcclusionShading::Update with pre-illumination on
@@ -2026,6 +2033,7 @@ cvr_status cvr_set_extinction_sat(cvr_ctx* ctx, const float* ext_lut, int lut_n)
   if (w > 4096 || h > 4096 || d > 4096 || cells >= ((size_t)1 << 31))
     return fail(c, CVR_ERR_ARG, "cvr_set_extinction_sat: volume too large for the SAT");
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
+  light_cache_drop(c);   // an EBS light cache holds this SAT's occlusion and shadow
   // Same grid as the last build (a TF change): rebuild into the existing buffers.
   // Freeing and re-allocating the ~30 GB of a 1024^3 SAT costs seconds.
   const bool same = c->d_sat && c->sat_dims[0] == w && c->sat_dims[1] == h && c->sat_dims[2] == d;
@@ -2140,24 +2148,32 @@ cvr_status cvr_copy_extinction_sat(cvr_ctx* ctx, float* out, size_t capacity, in
   return CVR_OK;
 }
 
-cvr_status cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_params* p,
-                             const cvr_output* o) {
-  Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (c && c->group)
-    return cvr::group_render(c, f, 1, o, [&](cvr_ctx* _m, const cvr_frame* mf, int, const cvr_output* mo) {
-      return cvr_render_extbsd(_m, mf, p, mo);
-    });
-  if (!c) return CVR_ERR_ARG;
-  if (!f || !p || !o || !o->rgba) return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: null argument");
+// dir_cone_max_distance = 0.75f * Dv (ebsrenderer.cpp:98-105, float arithmetic)
+// unless the caller gives one
+static float ebs_max_distance(const Ctx* c, const cvr_ebs_params* p) {
+  if (p->shadow_max_distance > 0.0f) return p->shadow_max_distance;
+  const float vw = (float)((double)c->N[0] * (double)c->scale[0]);
+  const float vh = (float)((double)c->N[1] * (double)c->scale[1]);
+  const float vd = (float)((double)c->N[2] * (double)c->scale[2]);
+  return 0.75f * std::sqrt((vw * vw + vh * vh) + vd * vd);
+}
+
+// The EbsArgs of a frame: the checks the EBS entry points share and the shader's
+// uniforms.  f == o == null: no frame is rendered (cvr_compute_light_cache_extbsd),
+// so the frame, output and gradient checks do not apply and of Q.a only the
+// volume box, the light and filter_bits are filled.
+static cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_ebs_params* p,
+                              const cvr_output* o, cvr::EbsArgs& Q, int& ntiles, size_t& npix) {
+  if (!p || (o && (!f || !o->rgba))) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
   if (c->filter_bits && c->sat_layout != 0)
-    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: filter_bits %d needs sat_layout 0 (the cell4 copy)",
+    return fail(c, CVR_ERR_ARG, "%s: filter_bits %d needs sat_layout 0 (the cell4 copy)", who,
                 c->filter_bits);
-  if (o->format != CVR_FORMAT_RGBA32F && o->format != CVR_FORMAT_RGBA16F)
-    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: unknown output format %d", o->format);
-  if (f->width < 1 || f->height < 1 || f->width > 32768 || f->height > 32768)
-    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: bad viewport %dx%d", f->width, f->height);
-  if (!c->d_cells || !c->d_tf) return fail(c, CVR_ERR_STATE, "cvr_render_extbsd: no volume or TF");
-  if (!c->d_sat) return fail(c, CVR_ERR_STATE, "cvr_render_extbsd: needs cvr_set_extinction_sat");
+  if (o && o->format != CVR_FORMAT_RGBA32F && o->format != CVR_FORMAT_RGBA16F)
+    return fail(c, CVR_ERR_ARG, "%s: unknown output format %d", who, o->format);
+  if (o && (f->width < 1 || f->height < 1 || f->width > 32768 || f->height > 32768))
+    return fail(c, CVR_ERR_ARG, "%s: bad viewport %dx%d", who, f->width, f->height);
+  if (!c->d_cells || (o && !c->d_tf)) return fail(c, CVR_ERR_STATE, "%s: no volume or TF", who);
+  if (!c->d_sat) return fail(c, CVR_ERR_STATE, "%s: needs cvr_set_extinction_sat", who);
   if (c->sat_layout == 0 && !c->d_sat_cells) {   // switched back to the cell4 copy: build it
     const int w = c->sat_dims[0], h = c->sat_dims[1], d = c->sat_dims[2];
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2165,26 +2181,33 @@ cvr_status cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_par
     const hipError_t e = cvr::launch_sat_cells(*c, c->d_sat, c->d_sat_cells, c->stream);
     if (e != hipSuccess) {   // never leave an unbuilt copy behind for the next frame to read
       void* q = c->d_sat_cells; free_dev(q); c->d_sat_cells = nullptr;
-      return fail(c, CVR_ERR_HIP, "cvr_render_extbsd: cell4 SAT build: %s", hipGetErrorString(e));
+      return fail(c, CVR_ERR_HIP, "%s: cell4 SAT build: %s", who, hipGetErrorString(e));
     }
   }
-  const bool phong = p->apply_gradient_shading != 0;
-  if (phong && !c->d_grad) return fail(c, CVR_ERR_STATE, "cvr_render_extbsd: Phong needs cvr_set_gradient");
-  if (p->shadow_type < 0 || p->shadow_type > 1) return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: bad shadow type");
+  const bool phong = o && p->apply_gradient_shading != 0;
+  if (phong && !c->d_grad) return fail(c, CVR_ERR_STATE, "%s: Phong needs cvr_set_gradient", who);
+  if (p->shadow_type < 0 || p->shadow_type > 1) return fail(c, CVR_ERR_ARG, "%s: bad shadow type", who);
   if (p->apply_occlusion && p->occlusion_shells < 1)
-    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: need >= 1 occlusion shell");
+    return fail(c, CVR_ERR_ARG, "%s: need >= 1 occlusion shell", who);
   if (p->apply_shadow && !(p->shadow_sample_interval > 0.0f))
-    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: shadow sample interval must be positive");
-  if (f->nranks > 1 && (f->tile_size < 16 || f->tile_size % 16 != 0 || f->rank < 0 || f->rank >= f->nranks))
-    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: bad tiling");
+    return fail(c, CVR_ERR_ARG, "%s: shadow sample interval must be positive", who);
+  if (o && f->nranks > 1 && (f->tile_size < 16 || f->tile_size % 16 != 0 || f->rank < 0 || f->rank >= f->nranks))
+    return fail(c, CVR_ERR_ARG, "%s: bad tiling", who);
   HIP_TRY(c, hipSetDevice(c->device));
 
-  cvr::EbsArgs Q{};
-  int ntiles = 0;
-  size_t npix = 0;
-  fill_frame_args(c, f, p->step, Q.a, ntiles, npix);
+  Q = cvr::EbsArgs{};
+  ntiles = 0;
+  npix = 0;
+  if (o) {
+    fill_frame_args(c, f, p->step, Q.a, ntiles, npix);
+  } else {
+    for (int i = 0; i < 3; i++) {
+      Q.a.half_grid[i] = ((float)c->N[i] * c->scale[i]) * 0.5f;   // as fill_frame_args
+      Q.a.N[i] = c->N[i];
+    }
+  }
   Q.a.filter_bits = c->filter_bits;   // GL_LINEAR weights of every fetch (CVR-SPEC-8 at 8)
-  if (c->cell_skip > 0) {   // the per-cell skip flags in the count / emit march
+  if (o && c->cell_skip > 0) {   // the per-cell skip flags in the count / emit march
     const cvr_status st = cell_flags_or_off(c);
     if (st == CVR_OK) {
       Q.a.cell_skip = 1;
@@ -2193,7 +2216,7 @@ cvr_status cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_par
       return st;
     }
   }
-  Q.a.out_half = o->format == CVR_FORMAT_RGBA16F;
+  Q.a.out_half = o && o->format == CVR_FORMAT_RGBA16F;
   Q.a.ka = p->ka; Q.a.kd = p->kd; Q.a.ks = p->ks;
   Q.a.shininess = p->shininess;
   for (int i = 0; i < 3; i++) { Q.a.ispec[i] = p->ispecular[i]; Q.a.light[i] = p->light_pos[i]; }
@@ -2232,23 +2255,143 @@ cvr_status cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_par
   Q.interval = p->shadow_sample_interval;
   Q.initial_step = p->shadow_initial_step;
   Q.ui_weight = p->shadow_ui_weight;
-  if (p->shadow_max_distance > 0.0f) {
-    Q.max_distance = p->shadow_max_distance;
-  } else {
-    // dir_cone_max_distance = 0.75f * Dv (ebsrenderer.cpp:98-105, float arithmetic)
-    const float vw = (float)((double)c->N[0] * (double)c->scale[0]);
-    const float vh = (float)((double)c->N[1] * (double)c->scale[1]);
-    const float vd = (float)((double)c->N[2] * (double)c->scale[2]);
-    Q.max_distance = 0.75f * std::sqrt((vw * vw + vh * vh) + vd * vd);
-  }
+  Q.max_distance = ebs_max_distance(c, p);
   // ShadeSample (:502-518): ka only with occlusion, kd/ks only with shadows
   Q.ka = Q.apply_occlusion ? p->ka : 0.0f;
   Q.kd = Q.apply_shadow ? p->kd : 0.0f;
   Q.ks = Q.apply_shadow ? p->ks : 0.0f;
+  return CVR_OK;
+}
+
+cvr_status cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_params* p,
+                             const cvr_output* o) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (c && c->group)
+    return cvr::group_render(c, f, 1, o, [&](cvr_ctx* _m, const cvr_frame* mf, int, const cvr_output* mo) {
+      return cvr_render_extbsd(_m, mf, p, mo);
+    });
+  if (!c) return CVR_ERR_ARG;
+  if (!f || !p || !o || !o->rgba) return fail(c, CVR_ERR_ARG, "cvr_render_extbsd: null argument");
+  cvr::EbsArgs Q;
+  int ntiles = 0;
+  size_t npix = 0;
+  const cvr_status st = ebs_prepare(c, "cvr_render_extbsd", f, p, o, Q, ntiles, npix);
+  if (st != CVR_OK) return st;
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t st) {
     return cvr::launch_ebs(*c, Q, out, smp, shade, ts, st);
   }, c->shade_flat != 0);
+}
+
+// ---------------------------------------------------------------------------
+// Pre-illumination of the EBS renderer: the SAT light cache (ebs_lightcache.hip)
+// and the cached march it shares with the DOS renderer (lightcache.hip)
+// ---------------------------------------------------------------------------
+
+static void ebs_light_cache_key(const Ctx* c, const cvr_ebs_params* p, const int dims[3],
+                                Ctx::LightCacheKey& k) {
+  k = Ctx::LightCacheKey{};
+  k.valid = 1;
+  k.kind = 1;
+  for (int i = 0; i < 3; i++) k.dims[i] = dims[i];
+  k.apply_occlusion = p->apply_occlusion != 0;
+  k.apply_shadow = p->apply_shadow != 0;
+  k.filter_bits = c->filter_bits;
+  // a term that is switched off does not reach the cache; the camera never does
+  if (k.apply_occlusion) {
+    k.ebs_shells = p->occlusion_shells;
+    k.ebs_radius = p->occlusion_radius;
+  }
+  if (k.apply_shadow) {
+    k.shadow_type = p->shadow_type;
+    k.ebs_angle = p->shadow_cone_angle_deg;
+    k.ebs_interval = p->shadow_sample_interval;
+    k.ebs_initial = p->shadow_initial_step;
+    k.ebs_weight = p->shadow_ui_weight;
+    k.ebs_max_distance = ebs_max_distance(c, p);
+    for (int i = 0; i < 3; i++) {
+      if (p->shadow_type == 0) k.light.position[i] = p->light_pos[i];
+      else k.light.forward[i] = p->light_forward[i];
+    }
+  }
+}
+
+// RC1PExtinctionBasedShading's PreComputeLightCache (the dispatch of
+// rc1pextbsd/lightcachecomputation.comp), queued on the context stream.
+static cvr_status ebs_light_cache_compute(Ctx* c, const char* who, const cvr_ebs_params* p,
+                                          const int dims[3]) {
+  if (!light_cache_dims_ok(dims))
+    return fail(c, CVR_ERR_ARG, "%s: light cache dimensions must be in [2, %d]", who, cvr::kMaxLightCacheDim);
+  cvr::EbsArgs Q;
+  int ntiles = 0;
+  size_t npix = 0;
+  cvr_status st = ebs_prepare(c, who, nullptr, p, nullptr, Q, ntiles, npix);
+  if (st != CVR_OK) return st;
+  if (c->native_exp)
+    return fail(c, CVR_ERR_ARG, "%s: the light cache has no native_exp (tolerance) form", who);
+  if ((st = light_cache_write_begin(c)) != CVR_OK) return st;
+  if ((st = light_cache_reserve(c, dims)) != CVR_OK) return st;
+  cvr::LightCacheArgs P{};
+  for (int i = 0; i < 3; i++) {
+    P.dims[i] = dims[i];
+    // VolumeScales * (VolumeDimensions / LightCacheDimensions), float
+    P.vs[i] = c->scale[i] * ((float)c->N[i] / (float)dims[i]);
+  }
+  c->lc_key.valid = 0;
+  HIP_TRY(c, cvr::launch_ebs_light_cache(*c, Q, P, c->d_lcache, c->stream));
+  if (!c->lc_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lc_ev, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->lc_ev, c->stream));
+  c->lc_written = true;
+  c->lc_writer = c->stream;
+  c->lc_builds++;
+  ebs_light_cache_key(c, p, dims, c->lc_key);
+  return CVR_OK;
+}
+
+cvr_status cvr_compute_light_cache_extbsd(cvr_ctx* ctx, const cvr_ebs_params* p, const int dims[3]) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_compute_light_cache_extbsd");
+  return ebs_light_cache_compute(c, "cvr_compute_light_cache_extbsd", p, dims);
+}
+
+// RC1PExtinctionBasedShading::Update with pre-illumination on: PreComputeLightCache,
+// then the cached march (obj_ray_marching.comp, the DOS renderer's too).  The
+// reference recomputes on every Update; here the compute is skipped while nothing
+// the cache depends on has changed, and the camera is nothing it depends on.
+cvr_status cvr_render_extbsd_preillum(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_params* p,
+                                      const int dims[3], const cvr_output* o) {
+  Ctx* c = reinterpret_cast<Ctx*>(ctx);
+  if (!c) return CVR_ERR_ARG;
+  NO_GROUP(c, "cvr_render_extbsd_preillum");
+  if (!f || !p || !o || !o->rgba) return fail(c, CVR_ERR_ARG, "cvr_render_extbsd_preillum: null argument");
+  if (!light_cache_dims_ok(dims))
+    return fail(c, CVR_ERR_ARG, "cvr_render_extbsd_preillum: light cache dimensions must be in [2, %d]",
+                cvr::kMaxLightCacheDim);
+  bool fresh = c->d_lcache && c->lc_key.valid;
+  if (fresh) {
+    Ctx::LightCacheKey k;
+    ebs_light_cache_key(c, p, dims, k);
+    fresh = std::memcmp(&k, &c->lc_key, sizeof(k)) == 0;
+  }
+  if (!fresh) {
+    const cvr_status st = ebs_light_cache_compute(c, "cvr_render_extbsd_preillum", p, dims);
+    if (st != CVR_OK) return st;
+  }
+  // the march reads the step, the Phong switch and constants, the light position
+  // and the two switches: cvr_render_preillum's own inputs
+  cvr_dos_params dp{};
+  dp.step = p->step;
+  dp.apply_gradient_shading = p->apply_gradient_shading;
+  dp.ka = p->ka; dp.kd = p->kd; dp.ks = p->ks;
+  dp.shininess = p->shininess;
+  for (int i = 0; i < 3; i++) {
+    dp.ispecular[i] = p->ispecular[i];
+    dp.light.position[i] = p->light_pos[i];
+  }
+  dp.apply_occlusion = p->apply_occlusion;
+  dp.apply_shadow = p->apply_shadow;
+  return preillum_march(c, "cvr_render_extbsd_preillum", f, &dp, o);
 }
 
 

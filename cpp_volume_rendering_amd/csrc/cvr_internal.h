@@ -138,14 +138,15 @@ struct DosArgs {
 
 // Pre-illumination (lightcache.hip): the light cache is an RG16F 3D image, one
 // uint32 per voxel (Idao in the low half, Idcs in the high half), x-fastest.
-// Its producer is the DOS cone kernel today; any producer that fills the same
-// image (cvr_set_light_cache) feeds the same march.
+// Its producers are the DOS cone kernel (lightcache.hip) and the EBS SAT kernel
+// (ebs_lightcache.hip); any producer that fills the same image
+// (cvr_set_light_cache) feeds the same march.
 constexpr int kMaxLightCacheDim = 512;
 struct LightCacheArgs {              // the computation's own uniforms (DosArgs holds the rest)
   int dims[3];                       // LightCacheDimensions
   int nb[3];                         // 4x4x4 voxel blocks per axis (set by the launcher)
   float vs[3];                       // VolumeScales * (VolumeDimensions / LightCacheDimensions)
-  float cam_up[3];                   // EyeCamUp (Camera::GetCameraVectors' cup)
+  float cam_up[3];                   // EyeCamUp (Camera::GetCameraVectors' cup; the DOS producer only)
 };
 struct LightCacheView {              // what the cached march's fetch reads
   const uint32_t* rg;
@@ -390,15 +391,21 @@ struct Ctx {
   int lc_dims[3] = {0, 0, 0};
   size_t lc_bytes = 0;
   int lc_builds = 0;                 // computes so far (option "light_cache_builds", read-only)
-  // what the cache was computed from (cvr_render_dosct_preillum skips the compute
-  // when nothing of it changed); invalid after cvr_set_light_cache
+  // what the cache was computed from (cvr_render_dosct_preillum and
+  // cvr_render_extbsd_preillum skip the compute when nothing of it changed);
+  // invalid after cvr_set_light_cache.  Compared as bytes: 4-byte members only.
   struct LightCacheKey {
     int valid = 0;
+    int kind = 0;                      // the producer: 0 DOS cones, 1 EBS SAT
     int dims[3] = {0, 0, 0};
     int apply_occlusion = 0, apply_shadow = 0, shadow_type = 0, filter_bits = 0;
-    cvr_cone_params cone[2] = {};
-    cvr_light light = {};
-    float eye[3] = {0, 0, 0}, cam_up[3] = {0, 0, 0};   // compared only with occlusion on
+    cvr_cone_params cone[2] = {};      // DOS
+    cvr_light light = {};              // DOS; EBS: position (type 0) or forward (type 1) only
+    float eye[3] = {0, 0, 0}, cam_up[3] = {0, 0, 0};   // DOS, compared only with occlusion on
+    // EBS: the AO parameters (occlusion on) and the shadow chain's (shadow on)
+    int ebs_shells = 0;
+    float ebs_radius = 0, ebs_angle = 0, ebs_interval = 0, ebs_initial = 0, ebs_weight = 0,
+          ebs_max_distance = 0;
   } lc_key;
   // frames that read the cache since it was last written: on one stream (a later
   // write on that stream is ordered behind them) or on several (the write drains
@@ -497,6 +504,9 @@ hipError_t launch_dos(const Ctx& c, const DosArgs& q, float4* out, uint32_t* sam
 // lightcache.hip: the light cache of the DOS cones, and the march that reads a cache
 hipError_t launch_light_cache(const DosArgs& q, const LightCacheArgs& p, const uint4* ext,
                               uint32_t* out, hipStream_t s);
+// ebs_lightcache.hip: the light cache of the EBS SAT terms (the context's SAT in its sat_layout)
+hipError_t launch_ebs_light_cache(const Ctx& c, const EbsArgs& q, const LightCacheArgs& p, uint32_t* out,
+                                  hipStream_t s);
 hipError_t launch_preillum(const Ctx& c, const DosArgs& q, const LightCacheView& v, float4* out,
                            uint32_t* samples, unsigned long long* shade,
                            unsigned long long* tile_samples, hipStream_t s);

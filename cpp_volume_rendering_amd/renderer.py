@@ -341,6 +341,14 @@ class Device:
                                                       ctypes.byref(params), d),
                 "cvr_compute_light_cache_dosct", self.handle)
 
+    def compute_light_cache_extbsd(self, params: N.EbsParams, dims=(32, 32, 32)):
+        """The EBS renderer's PreComputeLightCache (rc1pextbsd/lightcachecomputation.comp):
+        the SAT occlusion and box-chain shadow of `params` once per voxel of a dims cache,
+        queued on the device's stream.  No frame: the cache does not depend on the camera."""
+        d = (ctypes.c_int * 3)(*[int(v) for v in dims])
+        N.check(N.lib().cvr_compute_light_cache_extbsd(self.handle, ctypes.byref(params), d),
+                "cvr_compute_light_cache_extbsd", self.handle)
+
     def set_light_cache(self, rg_half: np.ndarray):
         """Upload a (dz, dy, dx, 2) cache of binary16 (Idao, Idcs) pairs (float16, or
         their uint16 bit patterns)."""
@@ -723,8 +731,13 @@ class RC1PExtinctionBasedShading(RayCasting1Pass):
 
     POINT_LIGHT, DIRECTIONAL_LIGHT = 0, 1
 
-    def __init__(self, device: int = 0, devices=None):
+    def __init__(self, device: int = 0, devices=None, pre_illumination: bool = False,
+                 light_cache_resolution=(32, 32, 32)):
         super().__init__(device, devices)
+        # "Use Pre-Illumination" (m_pre_illum_str_vol, ebsrenderer.cpp:46-47): the SAT
+        # occlusion and shadow once per voxel of a light cache, one fetch per sample
+        self.pre_illumination = bool(pre_illumination)
+        self.light_cache_resolution = tuple(int(v) for v in light_cache_resolution)
         self.apply_ambient_occlusion = True          # ebsrenderer.cpp:27-31
         self.ambient_occlusion_shells = 15
         self.ambient_occlusion_radius = 1.0
@@ -774,6 +787,15 @@ class RC1PExtinctionBasedShading(RayCasting1Pass):
         return True
 
     _ENTRY = "cvr_render_extbsd"
+
+    def render_to(self, frame: N.Frame, out: N.Output):
+        if not self.pre_illumination:
+            return super().render_to(frame, out)
+        dims = (ctypes.c_int * 3)(*[int(v) for v in self.light_cache_resolution])
+        N.check(N.lib().cvr_render_extbsd_preillum(self.device.handle, ctypes.byref(frame),
+                                                   ctypes.byref(self._params), dims,
+                                                   ctypes.byref(out)),
+                "cvr_render_extbsd_preillum", self.device.handle)
 
 
 class RayCasting1PassIsoAdapt(RayCasting1Pass):

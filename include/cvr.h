@@ -40,6 +40,10 @@
  *   cvr_render_extbsd            <- RC1PExtinctionBasedShading::Update + Redraw
  *                                   cppvolrend/structured/rc1pextbsd/ebsrenderer.cpp:125-260
  *                                   (the dispatch of ebs_ray_bbox_marching.comp)
+ *   cvr_render_extbsd_preillum   <- the same Update with "Use Pre-Illumination" on
+ *                                   (ebsrenderer.cpp:46-47): PreComputeLightCache
+ *                                   (rc1pextbsd/lightcachecomputation.comp) +
+ *                                   _common_shaders/obj_ray_marching.comp
  *   cvr_status (never exit())    <- gl::ExitOnGLError  libs/gl_utils/utils.cpp:11-30
  *
  * Threading: one context per device, externally synchronised (the reference
@@ -440,7 +444,7 @@ cvr_status  cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* frame,
  * cone traces, and composites a sample only when occlusion or shadow is on.  An
  * approximation, in the reference too: the image differs from cvr_render_dosct's
  * (DESIGN.md §5b′ gives SSIM per cache resolution).  A new volume, transfer
- * function or extinction pyramid drops the cache.  Group contexts
+ * function, extinction pyramid or SAT drops the cache.  Group contexts
  * (cvr_create_group) refuse these calls with CVR_ERR_STATE.
  * -------------------------------------------------------------------------- */
 
@@ -452,8 +456,12 @@ cvr_status  cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* frame,
  * form). */
 cvr_status  cvr_compute_light_cache_dosct(cvr_ctx* ctx, const cvr_frame* frame,
                                           const cvr_dos_params* params, const int dims[3]);
-/* Upload a cache computed elsewhere (tests; a later producer such as the EBS
- * light cache): 2 * dims[0] * dims[1] * dims[2] binary16 values. */
+/* Upload a cache computed elsewhere (tests, or a producer of the caller's own):
+ * 2 * dims[0] * dims[1] * dims[2] binary16 values.  The library's two producers
+ * are cvr_compute_light_cache_dosct and cvr_compute_light_cache_extbsd; all
+ * three fill the one cache object of the context, which cvr_render_preillum
+ * marches over.  An uploaded cache is never taken for a computed one: the next
+ * cvr_render_dosct_preillum / cvr_render_extbsd_preillum computes its own. */
 cvr_status  cvr_set_light_cache(cvr_ctx* ctx, const uint16_t* rg_half, const int dims[3]);
 /* Copy the cache back after draining the context stream; capacity counts
  * binary16 values.  out = NULL: dims only. */
@@ -502,6 +510,39 @@ cvr_status  cvr_sat_layout_check(const int sat_dims[3], int layout, int pad_plan
  * cvr_set_extinction_sat. */
 cvr_status  cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* frame,
                               const cvr_ebs_params* params, const cvr_output* out);
+
+/* ----------------------------------------------------------------------------
+ * Pre-illumination of the EBS renderer: the same switch (ebsrenderer.cpp:46-47)
+ * and the same cache object and march as the DOS renderer's above.  The SAT
+ * ambient occlusion and the SAT box-chain shadow are evaluated once per voxel
+ * of the light cache (rc1pextbsd/lightcachecomputation.comp), at the voxel
+ * centre, with the arithmetic of cvr_render_extbsd's shader; the march then
+ * fetches the cache once per sample.  Neither term reads the camera (the boxes
+ * are centred on the voxel, the chain points at the light), so an EBS cache
+ * survives every camera motion.  A new volume, transfer function or SAT drops
+ * the cache.  Group contexts refuse these calls with CVR_ERR_STATE.
+ * -------------------------------------------------------------------------- */
+
+/* PreComputeLightCache: fills a cache of dims[3] voxels (each in [2, 512]) with
+ * the occlusion and shadow of `params`, queued on the context stream.  It takes
+ * no frame: nothing camera-dependent reaches the cache.  Needs the volume and
+ * cvr_set_extinction_sat (else CVR_ERR_STATE).  Honours sat_layout and
+ * filter_bits as cvr_render_extbsd does (filter_bits 8 with sat_layout 1 is
+ * CVR_ERR_ARG); with option native_exp set it returns CVR_ERR_ARG, as the DOS
+ * compute.  Counted by "light_cache_builds". */
+cvr_status  cvr_compute_light_cache_extbsd(cvr_ctx* ctx, const cvr_ebs_params* params,
+                                           const int dims[3]);
+/* RC1PExtinctionBasedShading::Update with the switch on: compute, then march
+ * (cvr_render_preillum's march, fed the step, the Blinn-Phong constants,
+ * light_pos and the two switches of `params`).  The compute is skipped while
+ * none of these changed since this context last computed: the producer (a DOS
+ * compute in between counts), the volume, the SAT, dims, the two switches,
+ * filter_bits, the occlusion parameters (occlusion on), the shadow parameters
+ * and light_pos (type 0) or light_forward (type 1) (shadow on).  The camera is
+ * not among them: an orbit around a fixed light computes once. */
+cvr_status  cvr_render_extbsd_preillum(cvr_ctx* ctx, const cvr_frame* frame,
+                                       const cvr_ebs_params* params, const int dims[3],
+                                       const cvr_output* out);
 
 /* The reference renderers' default parameters for `variant`. */
 void        cvr_iso_params_default(int variant, cvr_iso_params* out);

@@ -182,8 +182,24 @@ HipExtinctionBasedShading::HipExtinctionBasedShading ()
   , dir_shadow_user_interface_weight(1.0f)
   , dir_cone_max_distance(0.0f)
   , type_of_shadow(0)
+  , pre_illumination(false)                    // m_pre_illum_str_vol.SetActive(false) (ebsrenderer.cpp:46)
+  , light_cache_resolution{32, 32, 32}         // SetLightCacheResolution(32, 32, 32) (:47)
   , m_params()
 {
+}
+
+void HipExtinctionBasedShading::SetPreIllumination (bool active)
+{
+  pre_illumination = active;
+  SetOutdated();
+}
+
+void HipExtinctionBasedShading::SetLightCacheResolution (int w, int h, int d)
+{
+  light_cache_resolution[0] = w;
+  light_cache_resolution[1] = h;
+  light_cache_resolution[2] = d;
+  SetOutdated();
 }
 
 // The SAT cells are GetExtN(value / max) of the CPU transfer function
@@ -244,8 +260,13 @@ bool HipExtinctionBasedShading::Update (vis::Camera* camera)
   return true;
 }
 
+// With pre-illumination on, Update's PreComputeLightCache and the cached march are
+// one library call; the EBS cache does not depend on the camera, so the library
+// recomputes it only when the light, the shading parameters, the volume or the SAT change.
 cvr_status HipExtinctionBasedShading::RenderFrame (const cvr_output* out)
 {
+  if (pre_illumination)
+    return cvr_render_extbsd_preillum(m_cvr, &frame_, &m_params, light_cache_resolution, out);
   return cvr_render_extbsd(m_cvr, &frame_, &m_params, out);
 }
 

@@ -94,6 +94,14 @@ public:
   float dir_cone_max_distance;
   int type_of_shadow;                  // 0 point, 1 directional
 
+  // m_pre_illum_str_vol (PreIlluminationStructuredVolume, ebsrenderer.cpp:46-47): the
+  // "Use Pre-Illumination" switch and the light cache's resolution, as
+  // HipDirOcclusionShading's.
+  bool pre_illumination;
+  int light_cache_resolution[3];
+  void SetPreIllumination (bool active);
+  void SetLightCacheResolution (int w, int h, int d);
+
 protected:
   cvr_status RenderFrame (const cvr_output* out) override;
   bool UploadExtinctionSAT ();         // GenerateExtinctionSAT3DTex (:624-723), on the GPU
