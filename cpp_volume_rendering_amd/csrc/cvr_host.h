@@ -1,0 +1,195 @@
+// cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
+// cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_iso.cpp)
+// share: error reporting, device-memory helpers, the half and vector helpers of
+// the host arithmetic, and the frame set-up common to the renderers.  Host only:
+// never included by a .hip file or a kernel header.
+//
+// Compiled with -ffp-contract=off: the arithmetic below feeds the kernels and
+// must be bit-reproducible (CVR-SPEC).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "cvr_internal.h"
+
+namespace cvr {
+
+// Stores the message in the context (cvr_last_error) and returns st.
+cvr_status fail(Ctx* c, cvr_status st, const char* fmt, ...);
+
+#define HIP_TRY(ctx, expr)                                                                    \
+  do {                                                                                        \
+    hipError_t _e = (expr);                                                                   \
+    if (_e != hipSuccess)                                                                     \
+      return ::cvr::fail(ctx, _e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,          \
+                         "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+  } while (0)
+
+// Before a state change writes or frees device state that frames read (volume
+// cells, TF, gradient, occupancy, cone tables, extinction pyramid, SAT): frames
+// may be in flight on any render stream the caller rotates (non-blocking
+// streams do not wait for the null-stream copies below), so the whole device
+// drains first.  The reference's equivalent is the GL pipeline's implicit
+// ordering on Init after a TF change (renderingmanager.cpp:1050-1127).
+#define QUIESCE(c)                             \
+  do {                                         \
+    HIP_TRY(c, hipSetDevice((c)->device));     \
+    HIP_TRY(c, hipDeviceSynchronize());        \
+  } while (0)
+
+// The multi-device split of this path is not built: a group context refuses it.
+#define NO_GROUP(c, who)                                                                       \
+  do {                                                                                         \
+    if ((c)->group)                                                                            \
+      return ::cvr::fail(c, CVR_ERR_STATE,                                                     \
+                         who ": not available on a group context (cvr_create_group)");         \
+  } while (0)
+
+template <class T>
+void free_dev(T*& p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
+}
+
+// float -> binary16 bits, round to nearest even (the GL driver's conversion of
+// GL_FLOAT client data to a 16F internal format).
+inline uint16_t to_half_bits(float f) {
+  _Float16 h = (_Float16)f;
+  uint16_t b;
+  std::memcpy(&b, &h, 2);
+  return b;
+}
+inline float half_round(float f) {
+  _Float16 h = (_Float16)f;
+  return (float)h;
+}
+inline float half_to_float_host(uint16_t b) {
+  _Float16 h;
+  std::memcpy(&h, &b, 2);
+  return (float)h;
+}
+
+struct V3 { float x, y, z; };
+inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+inline V3 cross(V3 x, V3 y) {
+  return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y};
+}
+inline float gdot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+inline V3 gnormalize(V3 v) {
+  float inv = 1.0f / std::sqrt(v.x * v.x + v.y * v.y + v.z * v.z);
+  return {v.x * inv, v.y * inv, v.z * inv};
+}
+
+// cvr_rc1pass.cpp: per-context resources and the frame constants every renderer uses
+cvr_status ensure_scratch(Ctx* c, size_t bytes);
+cvr_status counters_acquire(Ctx* c, hipStream_t s);
+cvr_status counters_release(Ctx* c, hipStream_t s);
+cvr_status ensure_occupancy(Ctx* c);
+cvr_status ensure_cell_flags(Ctx* c);
+cvr_status cell_flags_or_off(Ctx* c);
+void fill_frame_args(Ctx* c, const cvr_frame* f, float step, Rc1passArgs& A, int& ntiles,
+                     size_t& npix);
+
+// The checks of a frame and its output that every renderer makes, in this
+// order: the output buffer, its format, the viewport, and (tiling) the screen
+// split's tile size and rank.
+cvr_status check_frame_output(Ctx* c, const char* who, const cvr_frame* f, const cvr_output* o,
+                              bool tiling = true);
+
+// The Blinn-Phong constants of the surface term (ray_marching_1p.comp:48-81).
+void set_phong_constants(Rc1passArgs& A, float ka, float kd, float ks, float shininess,
+                         const float ispec[3], const float light[3]);
+
+// With option "cell_skip" on: the march uses the cells' skip flags at `level`
+// (built here when stale).  Without memory for the build the frame renders
+// without them (cell_flags_or_off); any other error is returned.
+cvr_status enable_cell_skip(Ctx* c, Rc1passArgs& A, int level);
+
+// cvr_lightcache.cpp: a new volume, TF, extinction pyramid or SAT drops the cache
+void light_cache_drop(Ctx* c);
+
+// cvr_dos.cpp, cvr_ebs.cpp: a frame's kernel arguments (also for the light cache)
+void resolve_cone_params(const Ctx* c, const cvr_dos_params* p, cvr_cone_params cp[2]);
+cvr_status dos_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_dos_params* p,
+                       const cvr_output* o, bool need_cones, DosArgs& Q, int& ntiles, size_t& npix,
+                       cvr_cone_params cp[2]);
+float ebs_max_distance(const Ctx* c, const cvr_ebs_params* p);
+cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_ebs_params* p,
+                       const cvr_output* o, EbsArgs& Q, int& ntiles, size_t& npix);
+
+// Output handling shared by the shaded renderers (device or host buffers, the
+// sample total through per-tile counts + the sum epilogue, kernel timing events,
+// shade counters).  launch(out, samples, shade, tile_samples, stream).
+template <class Launch>
+cvr_status render_shaded(Ctx* c, const cvr_output* o, int ntiles, size_t npix, const Launch& launch,
+                         bool flat_jobs = false) {
+  hipStream_t s = c->stream;
+  float4* d_out;
+  uint32_t* d_samples;
+  unsigned long long* d_total;
+  const size_t rgba_bytes = npix * (o->format == CVR_FORMAT_RGBA16F ? 8 : 16), smp_bytes = npix * 4;
+  if (o->on_device) {
+    d_out = (float4*)o->rgba;
+    d_samples = (uint32_t*)o->samples;
+    d_total = (unsigned long long*)o->total;
+  } else {
+    cvr_status st = ensure_scratch(c, rgba_bytes + (o->samples ? smp_bytes : 0));
+    if (st != CVR_OK) return st;
+    d_out = (float4*)c->d_scratch;
+    d_samples = o->samples ? (uint32_t*)((char*)c->d_scratch + rgba_bytes) : nullptr;
+    d_total = o->total ? c->d_total : nullptr;
+  }
+  // (flat shading keeps one job-list set per render stream: no wait for it here)
+  (void)flat_jobs;
+  const bool use_counters = d_total || c->shade_counters;
+  if (use_counters) {
+    cvr_status st = counters_acquire(c, s);
+    if (st != CVR_OK) return st;
+  }
+  if (d_total && !o->on_device) HIP_TRY(c, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
+  unsigned long long* tile_samples = nullptr;
+  if (d_total) {
+    if (c->tile_samples_n < ntiles) {
+      free_dev(c->d_tile_samples); c->tile_samples_n = 0;
+      HIP_TRY(c, hipMalloc((void**)&c->d_tile_samples, (size_t)ntiles * 8));
+      HIP_TRY(c, hipMemsetAsync(c->d_tile_samples, 0, (size_t)ntiles * 8, s));
+      c->tile_samples_n = ntiles;
+    }
+    tile_samples = c->d_tile_samples;
+  }
+  unsigned long long* shade = nullptr;
+  if (c->shade_counters) {
+    if (!c->d_shade) HIP_TRY(c, hipMalloc((void**)&c->d_shade, 3 * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(c->d_shade, 0, 3 * sizeof(unsigned long long), s));
+    shade = c->d_shade;
+  }
+  const size_t nev = c->ev_start.size();
+  const size_t slot = nev ? (size_t)(c->timed_frames % (long long)nev) : 0;
+  if (nev) HIP_TRY(c, hipEventRecord(c->ev_start[slot], s));
+  HIP_TRY(c, launch(d_out, d_samples, shade, tile_samples, s));
+  if (nev) {
+    HIP_TRY(c, hipEventRecord(c->ev_stop[slot], s));
+    c->timed_frames++;
+  }
+  if (tile_samples) {
+    RenderPlan plan{};
+    plan.ntiles = ntiles;
+    HIP_TRY(c, launch_tile_epilogue(nullptr, tile_samples, d_total, plan, nullptr, s));
+  }
+  if (use_counters) {
+    cvr_status st = counters_release(c, s);
+    if (st != CVR_OK) return st;
+  }
+  if (!o->on_device) {
+    HIP_TRY(c, hipMemcpyAsync(o->rgba, d_out, rgba_bytes, hipMemcpyDeviceToHost, s));
+    if (o->samples) HIP_TRY(c, hipMemcpyAsync(o->samples, d_samples, smp_bytes, hipMemcpyDeviceToHost, s));
+    if (o->total) HIP_TRY(c, hipMemcpyAsync(o->total, d_total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+  }
+  return CVR_OK;
+}
+
+}  // namespace cvr

@@ -1,5 +1,5 @@
-// cvr_internal.h — context state and kernel launch parameters shared by the
-// C-ABI implementation (cvr_api.cpp) and the gfx950 kernels (raymarch.hip).
+// cvr_internal.h — context state and kernel launch parameters shared by the C-ABI
+// implementation (cvr_*.cpp; host-only helpers: cvr_host.h) and the gfx950 kernels (*.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -5,7 +5,7 @@ Init again (renderingmanager.cpp:1050-1127, rc1prenderer.cpp:50-70); GL orders t
 change after every draw already issued.  Here frames may still be queued on any of
 the non-blocking streams a caller rotates (screen_tiles.ScreenTileSplit), so every
 state setter drains the device before it writes or frees state frames read
-(cvr_api.cpp QUIESCE).  Each test queues frames on 3 non-blocking streams behind a
+(cvr_host.h QUIESCE).  Each test queues frames on 3 non-blocking streams behind a
 spin kernel (so they are certainly still pending), changes the state, renders the
 next frame, and checks every in-flight frame against the oracle with the OLD state
 and the next frame against the oracle with the NEW state, bit for bit."""
