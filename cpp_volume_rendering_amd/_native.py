@@ -38,6 +38,8 @@ EXPORTED_SYMBOLS = (
     "cvr_render_preillum", "cvr_render_dosct_preillum",
     "cvr_tf1d_ext_lut", "cvr_set_extinction_sat", "cvr_copy_extinction_sat", "cvr_sat_layout_check", "cvr_render_extbsd",
     "cvr_compute_light_cache_extbsd", "cvr_render_extbsd_preillum",
+    "cvr_crtgt_params_default", "cvr_crtgt_build_rays", "cvr_crtgt_begin", "cvr_crtgt_advance",
+    "cvr_render_crtgt",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
     "cvr_decode_tiles", "cvr_comm_init_local", "cvr_create_group", "cvr_group_size",
@@ -128,6 +130,19 @@ class EbsParams(ctypes.Structure):
                 ("shadow_type", ctypes.c_int), ("shadow_cone_angle_deg", ctypes.c_float),
                 ("shadow_sample_interval", ctypes.c_float), ("shadow_initial_step", ctypes.c_float),
                 ("shadow_ui_weight", ctypes.c_float), ("shadow_max_distance", ctypes.c_float)]
+
+
+CRTGT_MAX_RAYS = 10000   # cvr.h CVR_CRTGT_MAX_RAYS
+
+
+class CrtgtParams(ctypes.Structure):
+    _fields_ = [("step", ctypes.c_float), ("apply_gradient_shading", ctypes.c_int),
+                ("ka", ctypes.c_float), ("kd", ctypes.c_float), ("ks", ctypes.c_float),
+                ("shininess", ctypes.c_float), ("light", Light),
+                ("light_gap", ctypes.c_float), ("light_step", ctypes.c_float),
+                ("apply_occlusion", ctypes.c_int), ("occ_distance", ctypes.c_float),
+                ("apply_shadow", ctypes.c_int), ("sdw_distance", ctypes.c_float),
+                ("shadow_type", ctypes.c_int)]
 
 
 class IsoParams(ctypes.Structure):
@@ -238,6 +253,12 @@ def lib() -> ctypes.CDLL:
         "cvr_compute_light_cache_extbsd": ([P, ctypes.POINTER(EbsParams), IP], I),
         "cvr_render_extbsd_preillum": ([P, ctypes.POINTER(Frame), ctypes.POINTER(EbsParams), IP,
                                         ctypes.POINTER(Output)], I),
+        "cvr_crtgt_params_default": ([ctypes.POINTER(CrtgtParams)], None),
+        "cvr_crtgt_build_rays": ([F, I, F, I, ctypes.c_uint, FP, FP], I),
+        "cvr_crtgt_begin": ([P, ctypes.POINTER(Frame), ctypes.POINTER(CrtgtParams), FP, I, FP, I], I),
+        "cvr_crtgt_advance": ([P, I, ctypes.POINTER(Output), ctypes.POINTER(ctypes.c_ulonglong)], I),
+        "cvr_render_crtgt": ([P, ctypes.POINTER(Frame), ctypes.POINTER(CrtgtParams), FP, I, FP, I,
+                              ctypes.POINTER(Output)], I),
         "cvr_iso_params_default": ([I, ctypes.POINTER(IsoParams)], None),
         "cvr_render_iso": ([P, ctypes.POINTER(Frame), ctypes.POINTER(IsoParams),
                             ctypes.POINTER(Output)], I),

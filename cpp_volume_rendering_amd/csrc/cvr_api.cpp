@@ -117,6 +117,7 @@ static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, in
   c->sat_dims[0] = c->sat_dims[1] = c->sat_dims[2] = 0;
   c->cone_valid = 0;
   light_cache_drop(c);
+  crtgt_invalidate(c);
   HIP_TRY(c, hipMalloc((void**)&c->d_lut, nv * sizeof(uint16_t)));
   uint16_t* d_lut = c->d_lut;
   hipError_t e = hipMemcpyAsync(d_lut, lut.data(), nv * sizeof(uint16_t), hipMemcpyHostToDevice,
@@ -282,6 +283,7 @@ void cvr_destroy(cvr_ctx* ctx) {
   free_dev(c->d_cones);
   delete[] c->cone_tab;
   light_cache_drop(c);
+  crtgt_release(c);
   if (c->lc_ev) (void)hipEventDestroy(c->lc_ev);
   free_dev(c->d_total);
   free_dev(c->d_scratch);
@@ -339,7 +341,7 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
     return b;
   }
   return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
-         c->lc_bytes;
+         c->lc_bytes + c->gt.bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {
@@ -385,6 +387,7 @@ cvr_status cvr_set_transfer_function(cvr_ctx* ctx, const float* rgbt, int n) {
   }
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
   light_cache_drop(c);
+  crtgt_invalidate(c);
   if (n != c->tf_n) {
     free_dev(c->d_tf);
     HIP_TRY(c, hipMalloc((void**)&c->d_tf, (size_t)n * 16));
@@ -417,6 +420,7 @@ cvr_status cvr_set_gradient(cvr_ctx* ctx, int mode) {
   if (mode != 0 && !c->d_vox) return fail(c, CVR_ERR_STATE, "cvr_set_gradient: no volume");
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
   free_dev(c->d_grad); c->grad_bytes = 0; c->grad_mode = 0;
+  crtgt_invalidate(c);
   if (mode == 0) return CVR_OK;
   c->grad_bytes = cvr::cell_count(c->cells) * 48;
   HIP_TRY(c, hipMalloc(&c->d_grad, c->grad_bytes));

@@ -179,5 +179,35 @@ cvr_status cvr_build_cone_tables(const cvr_cone_params* p, float sigma0, cvr_con
   return CVR_OK;
 }
 
+// The ray tables of RC1PConeLightGroundTruthSteps::Update (crtgtrenderer.cpp:131-184):
+// one generator, the occlusion table drawn first, two draws per ray.  The
+// reference's std::default_random_engine + uniform_real_distribution<float> are
+// platform-defined; the generator here is minstd_rand0 with the u of cvr.h.
+cvr_status cvr_crtgt_build_rays(float occ_aperture_deg, int n_occ, float sdw_aperture_deg, int n_sdw,
+                                unsigned seed, float* out_occ, float* out_sdw) {
+  if (n_occ < 0 || n_occ > CVR_CRTGT_MAX_RAYS || n_sdw < 0 || n_sdw > CVR_CRTGT_MAX_RAYS) return CVR_ERR_ARG;
+  if ((n_occ > 0 && !out_occ) || (n_sdw > 0 && !out_sdw)) return CVR_ERR_ARG;
+  unsigned long long x = seed % 2147483647u;
+  if (x == 0) x = 1;
+  auto draw = [&x]() {
+    x = (16807ull * x) % 2147483647ull;
+    return (float)((double)(x - 1) / 2147483646.0);
+  };
+  const float pi = 3.14159265358979323846f;   // glm::pi<float>()
+  const V3 gtray{0, 0, 1};
+  auto table = [&](float aperture, int n, float* out) {
+    for (int i = 0; i < n; i++) {
+      const float theta = draw() * (pi * (aperture / 180.f));
+      const float phi = draw() * (pi * (360.f / 180.f));
+      V3 v = rodrigues(gtray, theta, V3{0, 1, 0});
+      v = rodrigues(v, phi, gtray);
+      out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
+    }
+  };
+  table(occ_aperture_deg, n_occ, out_occ);
+  table(sdw_aperture_deg, n_sdw, out_sdw);
+  return CVR_OK;
+}
+
 #pragma GCC visibility pop
 }  // extern "C"

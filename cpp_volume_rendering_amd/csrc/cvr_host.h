@@ -1,5 +1,6 @@
 // cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
-// cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_iso.cpp)
+// cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_crtgt.cpp,
+// cvr_iso.cpp)
 // share: error reporting, device-memory helpers, the half and vector helpers of
 // the host arithmetic, and the frame set-up common to the renderers.  Host only:
 // never included by a .hip file or a kernel header.
@@ -110,6 +111,11 @@ cvr_status enable_cell_skip(Ctx* c, Rc1passArgs& A, int level);
 
 // cvr_lightcache.cpp: a new volume, TF, extinction pyramid or SAT drops the cache
 void light_cache_drop(Ctx* c);
+
+// cvr_crtgt.cpp: a new volume, TF or gradient ends the ground-truth frame in
+// progress; the context's end frees its state
+void crtgt_invalidate(Ctx* c);
+void crtgt_release(Ctx* c);
 
 // cvr_dos.cpp, cvr_ebs.cpp: a frame's kernel arguments (also for the light cache)
 void resolve_cone_params(const Ctx* c, const cvr_dos_params* p, cvr_cone_params cp[2]);

@@ -179,6 +179,33 @@ struct EbsArgs {
   float ka, kd, ks;                  // Kambient if occlusion, Kdiffuse/Kspecular if shadow, else 0
 };
 
+// Ground-truth cone ray-caster (crtgt.hip): the shader's uniforms, and the
+// progressive frame's device state.  A launch round marches at most
+// kCrtgtRoundSamples iterations per pixel, so the round's job storage is bounded.
+constexpr int kCrtgtRoundSamples = 4;
+struct CrtgtArgs {
+  Rc1passArgs a;                     // ray, volume, TF, eye, light position, shininess
+  float G[3];                        // VolumeGridSize
+  float light_gap, light_step;
+  int apply_occlusion, apply_shadow, shadow_type, phong;
+  float ka, kd, ks;                  // Ka if occlusion, Kd / Ks if shadow, else 0
+  float occ_distance, sdw_distance;
+  int n_occ, n_sdw;
+  const float* occ_rays;             // n x (r, g, b), binary16-rounded (device)
+  const float* sdw_rays;
+  float lzaxs[3], lup[3], lright[3]; // LightCamForward (= -light.forward), Up, Right
+};
+struct CrtgtState {
+  float4* dst = nullptr;             // per pixel: the composite so far
+  float* s = nullptr;                // the ray parameter of the next iteration
+  uint32_t* cnt = nullptr;           // loop iterations so far
+  uint32_t* done = nullptr;          // 1: the pixel's loop has ended
+  uint32_t* nj = nullptr;            // jobs of the current round
+  float4* jobs = nullptr;            // slot = pixel * kCrtgtRoundSamples + j: 2 float4 (+1 with Phong)
+  uint32_t* list = nullptr;          // the round's occupied slots, compacted
+  unsigned long long* ctr = nullptr; // [0] jobs of the round, [1] unfinished pixels, [2] iterations so far
+};
+
 // Isosurface ray-casters with block skipping (iso.hip): the shaders' uniforms.
 struct IsoArgs {
   Rc1passArgs a;                     // ray, volume, Blinn-Phong constants, tiles
@@ -416,6 +443,20 @@ struct Ctx {
   hipEvent_t lc_ev = nullptr;
   hipStream_t lc_writer = nullptr;
   bool lc_written = false;
+  // ground-truth cone ray-caster (cvr_crtgt.cpp): the progressive frame between
+  // cvr_crtgt_begin and its cvr_crtgt_advance calls
+  struct Crtgt {
+    bool valid = false;                // begun, and the volume, TF and gradient are still those
+    CrtgtArgs q{};
+    CrtgtState st;
+    float* d_rays = nullptr;           // both tables, occlusion first
+    size_t npix = 0;                   // pixels the state is allocated for
+    int job_f4 = 0;                    // float4 per job the storage is allocated for
+    size_t ray_cap = 0;                // rays d_rays holds
+    size_t bytes = 0;                  // all of the above (cvr_device_bytes)
+    int ntiles = 0;
+    unsigned long long unfinished = 0;
+  } gt;
   unsigned long long* d_tile_samples = nullptr;   // per-wave-tile sample counts (zeroed)
   int tile_samples_n = 0;
   // d_tile_samples and d_shade are one set per context: a frame that uses them on
@@ -510,6 +551,13 @@ hipError_t launch_ebs_light_cache(const Ctx& c, const EbsArgs& q, const LightCac
 hipError_t launch_preillum(const Ctx& c, const DosArgs& q, const LightCacheView& v, float4* out,
                            uint32_t* samples, unsigned long long* shade,
                            unsigned long long* tile_samples, hipStream_t s);
+// crtgt.hip: the ground-truth frame's state reset, one launch round of at most k
+// (<= kCrtgtRoundSamples) iterations per pixel (march, shade, fold), and the copy of
+// the state into an output image
+hipError_t launch_crtgt_init(const CrtgtArgs& q, const CrtgtState& st, hipStream_t s);
+hipError_t launch_crtgt_round(const Ctx& c, const CrtgtArgs& q, const CrtgtState& st, int k, hipStream_t s);
+hipError_t launch_crtgt_store(const CrtgtArgs& q, const CrtgtState& st, float4* out, uint32_t* samples,
+                              unsigned long long* total, int half, hipStream_t s);
 // iso.hip: raw per-block extremes (uint2), and the isosurface march (variant 0/1)
 hipError_t launch_block_minmax(const void* vox, int bpv, const int N[3], const int nb[3], uint2* out,
                                hipStream_t s);

@@ -370,6 +370,28 @@ class Device:
                 "cvr_copy_light_cache", self.handle)
         return a
 
+    def crtgt_begin(self, frame: N.Frame, params: N.CrtgtParams, occ_rays=None, sdw_rays=None):
+        """Resets the ground-truth frame's per-pixel state (cvr_crtgt_begin).  occ_rays /
+        sdw_rays: (n, 3) float tables (build_crtgt_rays); None for a term that is off."""
+        def table(r):
+            if r is None:
+                return None, None, 0
+            a = np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 3)
+            return a, N.fptr(a), a.shape[0]
+        occ, po, no = table(occ_rays)
+        sdw, ps, ns = table(sdw_rays)
+        N.check(N.lib().cvr_crtgt_begin(self.handle, ctypes.byref(frame), ctypes.byref(params),
+                                        po, no, ps, ns), "cvr_crtgt_begin", self.handle)
+
+    def crtgt_advance(self, max_samples: int, out: Optional[N.Output] = None) -> int:
+        """Extends every unfinished ray by at most max_samples iterations and copies the
+        current image to `out` (cvr_crtgt_advance).  Returns the pixels still unfinished."""
+        left = ctypes.c_ulonglong()
+        N.check(N.lib().cvr_crtgt_advance(self.handle, int(max_samples),
+                                          ctypes.byref(out) if out is not None else None,
+                                          ctypes.byref(left)), "cvr_crtgt_advance", self.handle)
+        return int(left.value)
+
     def device_bytes(self) -> int:
         return int(N.lib().cvr_device_bytes(self.handle))
 
@@ -796,6 +818,124 @@ class RC1PExtinctionBasedShading(RayCasting1Pass):
                                                    ctypes.byref(self._params), dims,
                                                    ctypes.byref(out)),
                 "cvr_render_extbsd_preillum", self.device.handle)
+
+
+def build_crtgt_rays(occ_aperture_deg: float, n_occ: int, sdw_aperture_deg: float, n_sdw: int,
+                     seed: int = 1):
+    """The ground-truth renderer's two ray tables (cvr_crtgt_build_rays: one minstd_rand0
+    stream, the occlusion table drawn first): ((n_occ, 3), (n_sdw, 3)) float32."""
+    occ = np.zeros((int(n_occ), 3), np.float32)
+    sdw = np.zeros((int(n_sdw), 3), np.float32)
+    N.check(N.lib().cvr_crtgt_build_rays(float(occ_aperture_deg), int(n_occ), float(sdw_aperture_deg),
+                                         int(n_sdw), int(seed), N.fptr(occ) if n_occ else None,
+                                         N.fptr(sdw) if n_sdw else None), "cvr_crtgt_build_rays")
+    return occ, sdw
+
+
+class RC1PConeLightGroundTruthSteps(RayCasting1Pass):
+    """HIP implementation of RC1PConeLightGroundTruthSteps
+    (cppvolrend/structured/rc1pcrtgt/crtgtrenderer.cpp): the march with every sample shaded
+    by secondary rays cast through the volume toward the eye (cone occlusion) and toward
+    the light (cone shadow).  The yardstick of the DOS / EBS approximations.
+
+    Progressive, as the reference: ``Update`` resets the frame (cvr_crtgt_begin) and every
+    ``Redraw`` extends each unfinished ray by ``samples_per_redraw`` iterations (the
+    reference: one) until ``frame_outdated`` turns False; further Redraws keep the image."""
+
+    POINT_LIGHT, SPOT_LIGHT, DIRECTIONAL_LIGHT = 0, 1, 2   # items_typelightsource (:547)
+
+    def __init__(self, device: int = 0, samples_per_redraw: int = 1, ray_seed: int = 1):
+        super().__init__(device)
+        self.samples_per_redraw = int(samples_per_redraw)
+        self.ray_seed = int(ray_seed)               # the generator's seed (cvr_crtgt_build_rays)
+        self.m_frame_outdated = True                # crtgtrenderer.cpp:30
+        self.m_show_frame_texture = False           # :31
+        self.m_u_step_size = 0.5                    # :32
+        self.m_apply_gradient = False               # :33
+        self.m_u_light_ray_initial_step = 1.0       # :35
+        self.m_u_light_ray_step_size = 0.5          # :36
+        self.m_light_parameters_outdated = True     # :38
+        self.m_apply_occlusion = False              # :40-44
+        self.m_occ_num_rays_sampled = 1
+        self.m_occ_cone_aperture_angle = 90.0
+        self.m_occ_cone_distance_eval = 100.0
+        self.m_apply_shadows = False                # :46-51
+        self.m_sdw_num_rays_sampled = 1
+        self.m_sdw_cone_aperture_angle = 1.0
+        self.m_sdw_cone_distance_eval = 100.0
+        self.m_shadow_type = self.POINT_LIGHT
+        self.occ_rays = self.sdw_rays = None        # the tables of the last Update
+        self._params = N.CrtgtParams()
+
+    def GetName(self): return "1-Pass - Ray Casting - Cone Ground Truth (Steps)"
+    def GetAbbreviationName(self): return "s_1rc_gt_c"
+
+    @property
+    def frame_outdated(self) -> bool:
+        return self.m_frame_outdated
+
+    def Init(self, swidth: int, sheight: int) -> bool:
+        if not super().Init(swidth, sheight):
+            return False
+        # GetDiagonal() * 0.50f / 0.75f (:110-114)
+        dm = self.m_ext_data_manager
+        d, h, w = dm.volume.shape
+        sc = [float(np.float32(s)) for s in dm.scale]
+        diag = math.sqrt((w * sc[0]) ** 2 + (h * sc[1]) ** 2 + (d * sc[2]) ** 2)
+        self.m_occ_cone_distance_eval = float(np.float32(diag * 0.50))
+        self.m_sdw_cone_distance_eval = float(np.float32(diag * 0.75))
+        return True
+
+    def SetOutdated(self):
+        super().SetOutdated()
+        self.m_frame_outdated = True
+
+    def SetLightParametersOutdated(self):
+        """After a change of a ray count or aperture: the next Update draws new tables."""
+        self.m_light_parameters_outdated = True
+        self.SetOutdated()
+
+    def Update(self, camera: Camera) -> bool:
+        rp = self.m_ext_rendering_parameters or RenderingParameters()
+        self._frame = self._camera_frame(camera)
+        if self.m_light_parameters_outdated or self.occ_rays is None:
+            self.occ_rays, self.sdw_rays = build_crtgt_rays(
+                self.m_occ_cone_aperture_angle, self.m_occ_num_rays_sampled,
+                self.m_sdw_cone_aperture_angle, self.m_sdw_num_rays_sampled, self.ray_seed)
+            self.m_light_parameters_outdated = False
+        p = self._params
+        N.lib().cvr_crtgt_params_default(ctypes.byref(p))
+        p.step = float(self.m_u_step_size)
+        p.apply_gradient_shading = int(bool(self.m_apply_gradient) and
+                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
+        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
+        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
+        p.light.position[:] = [float(v) for v in rp.light_position]
+        p.light.forward[:] = [float(v) for v in rp.light_forward]
+        p.light.up[:] = [float(v) for v in rp.light_up]
+        p.light.right[:] = [float(v) for v in rp.light_right]
+        p.light.spot_angle_deg = float(rp.spot_light_angle)
+        p.light_gap = float(self.m_u_light_ray_initial_step)
+        p.light_step = float(self.m_u_light_ray_step_size)
+        p.apply_occlusion = int(bool(self.m_apply_occlusion))
+        p.occ_distance = float(self.m_occ_cone_distance_eval)
+        p.apply_shadow = int(bool(self.m_apply_shadows))
+        p.sdw_distance = float(self.m_sdw_cone_distance_eval)
+        p.shadow_type = int(self.m_shadow_type)
+        s = torch.cuda.current_stream(self._device_index)
+        self.device.set_stream(s.cuda_stream)
+        self.device.crtgt_begin(self._frame, p, self.occ_rays if p.apply_occlusion else None,
+                                self.sdw_rays if p.apply_shadow else None)
+        self.m_frame_outdated = True
+        return True
+
+    def render_to(self, frame: N.Frame, out: N.Output):
+        """RedrawFrameTexture (:272-325): one more dispatch while the frame is outdated
+        (a converged frame is only copied)."""
+        self.m_frame_outdated = self.device.crtgt_advance(self.samples_per_redraw, out) > 0
+
+    def render_frames_to(self, frames, outs):
+        raise NotImplementedError(f"{type(self).__name__}: one frame per call")
 
 
 class RayCasting1PassIsoAdapt(RayCasting1Pass):

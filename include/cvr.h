@@ -44,6 +44,11 @@
  *                                   (ebsrenderer.cpp:46-47): PreComputeLightCache
  *                                   (rc1pextbsd/lightcachecomputation.comp) +
  *                                   _common_shaders/obj_ray_marching.comp
+ *   cvr_crtgt_begin / _advance   <- RC1PConeLightGroundTruthSteps::Update + RedrawFrameTexture
+ *   cvr_render_crtgt                cppvolrend/structured/rc1pcrtgt/crtgtrenderer.cpp:121-325
+ *                                   (the dispatches of gt_ray_marching.comp, one sample per
+ *                                   pixel each, until every pixel's state says "done")
+ *   cvr_crtgt_build_rays         <- the ray tables of Update, crtgtrenderer.cpp:131-184
  *   cvr_status (never exit())    <- gl::ExitOnGLError  libs/gl_utils/utils.cpp:11-30
  *
  * Threading: one context per device, externally synchronised (the reference
@@ -65,7 +70,7 @@ extern "C" {
  * (2: cvr_frame gained use_view/view).  Callers compare cvr_abi_version() with
  * the CVR_ABI_VERSION they were compiled against before the first call that
  * passes a struct.  Entry points that are only added (the pre-illumination
- * calls below) leave every existing caller valid and do not bump it; a caller
+ * and ground-truth calls below) leave every existing caller valid and do not bump it; a caller
  * that needs them looks them up by name. */
 #define CVR_ABI_VERSION 2
 
@@ -543,6 +548,93 @@ cvr_status  cvr_compute_light_cache_extbsd(cvr_ctx* ctx, const cvr_ebs_params* p
 cvr_status  cvr_render_extbsd_preillum(cvr_ctx* ctx, const cvr_frame* frame,
                                        const cvr_ebs_params* params, const int dims[3],
                                        const cvr_output* out);
+
+/* ----------------------------------------------------------------------------
+ * Ground-truth cone ray-caster: RC1PConeLightGroundTruthSteps ("1-Pass - Ray
+ * Casting - Cone Ground Truth (Steps)", s_1rc_gt_c; cppvolrend/structured/
+ * rc1pcrtgt/crtgtrenderer.cpp, gt_ray_marching.comp).  The yardstick of the DOS
+ * and EBS approximations: the march of cvr_render_rc1pass with every sample of
+ * alpha > 0 shaded by brute force, a bundle of secondary rays marched through
+ * the volume and the transfer function toward the eye (cone occlusion, :109-169)
+ * and a second bundle toward the light (cone shadow, :171-252); a ray's
+ * transmittance is the trapezoid rule over the TF's extinction at light_step
+ * intervals, starting light_gap away from the sample and stopping at the box,
+ * at the term's distance or at 99 % opacity, and a term is the mean of its rays'
+ * transmittances weighted by the cosine to the cone axis.  ShadeSample (:254-302)
+ * combines them as the DOS renderer does, with a white specular term.
+ *
+ * As written in the shader, the spot shadow (shadow_type 1) tests
+ * dot(v_dir, LightCamForward) < 30.0, which always holds: its shadow term is 0.0
+ * for every sample.  That is reproduced, as the (u, v) swap of the DOS shadow is.
+ *
+ * The frame is progressive, as in the reference, whose Redraw takes one sample per
+ * pixel: cvr_crtgt_begin resets a per-pixel state held by the context (ray
+ * parameter s, RGBA, iteration count, done flag: 32 bytes per pixel), and each
+ * cvr_crtgt_advance extends every unfinished ray.  Unlike the reference, which
+ * parks s and the colour in RG16F / RGBA16F images between dispatches, the state
+ * is float: the converged frame is the shader's arithmetic carried through in
+ * float and does not depend on how the march was cut into calls, and a pixel
+ * whose box lies behind the eye (D <= 0) is finished at once (DESIGN.md 5d').
+ * A new volume, transfer function or gradient invalidates the state.  Honours
+ * filter_bits; with option native_exp set these calls return CVR_ERR_ARG.  Group
+ * contexts (cvr_create_group) refuse them with CVR_ERR_STATE.
+ * -------------------------------------------------------------------------- */
+#define CVR_CRTGT_MAX_RAYS 10000      /* the reference UI's bound on either table      */
+#define CVR_CRTGT_MAX_RAY_STEPS 65536 /* most light_step intervals one secondary ray
+                                         may take, (distance - light_gap) / light_step */
+typedef struct cvr_crtgt_params {
+  float step;                  /* <= 0: 0.5/sqrt(3)*|scale| (crtgtrenderer.cpp:107-108) */
+  int   apply_gradient_shading;/* m_apply_gradient (needs cvr_set_gradient)             */
+  float ka, kd, ks, shininess; /* Blinn-Phong constants (renderingparameters.cpp:23-26) */
+  cvr_light light;             /* the current light source (forward = -LightCamForward) */
+  float light_gap, light_step; /* LightRayInitialGap 1.0, LightRayStepSize 0.5 (> 0)    */
+  int   apply_occlusion;       /* m_apply_occlusion (default 0)                         */
+  float occ_distance;          /* OccConeDistanceEvaluation; <= 0: diagonal * 0.50      */
+  int   apply_shadow;          /* m_apply_shadows (default 0)                           */
+  float sdw_distance;          /* SdwConeDistanceEvaluation; <= 0: diagonal * 0.75      */
+  int   shadow_type;           /* 0 point, 1 spot, 2 directional                        */
+} cvr_crtgt_params;
+/* The reference's defaults (crtgtrenderer.cpp:23-51, 107-113): step 0 (the default
+ * step), no Phong, (0.5, 0.5, 0.8, 30), light 0 of the reference's light list, gap
+ * 1.0, step 0.5, both terms off with distance 0 (the diagonal fractions), type 0. */
+void        cvr_crtgt_params_default(cvr_crtgt_params* out);
+/* The two ray tables of Update (:131-184), n x (r, g, b) floats each (out_occ /
+ * out_sdw may be NULL when its n is 0).  Touches no device.  One generator is drawn
+ * for the occlusion table first and then for the shadow table: per ray u1, u2 with
+ * theta = u1 * (pi * (aperture / 180)), phi = u2 * (pi * (360 / 180)) in float, and
+ * the vector Rodrigues(Rodrigues((0,0,1), theta, (0,1,0)), phi, (0,0,1)).  The
+ * reference's std::default_random_engine is platform-defined; this one is
+ * minstd_rand0: x <- 16807 x mod (2^31 - 1), x0 = seed (0 -> 1), and
+ * u = (float)((double)(x - 1) / 2147483646.0).  n in [0, CVR_CRTGT_MAX_RAYS]. */
+cvr_status  cvr_crtgt_build_rays(float occ_aperture_deg, int n_occ, float sdw_aperture_deg,
+                                 int n_sdw, unsigned seed, float* out_occ, float* out_sdw);
+/* Resets the per-pixel state for `frame` (a whole frame: nranks <= 1, else
+ * CVR_ERR_ARG) and keeps the parameters and the two ray tables (stored with RGB16F
+ * semantics: every coefficient rounded to binary16, as SetData(GL_RGB16F) +
+ * texelFetch).  n must be in [1, CVR_CRTGT_MAX_RAYS] for a term that is on (the
+ * reference's UI allows 0, which divides 0 by 0); the table of a term that is off
+ * is not read.  Needs the volume and the TF, and the gradient with Phong on (else
+ * CVR_ERR_STATE).  light_step must be > 0 and large enough to advance a float at
+ * the term's distance, and a ray may take at most CVR_CRTGT_MAX_RAY_STEPS steps.
+ * Device memory, all counted by cvr_device_bytes: 32 B per pixel of state, 24 B of
+ * counters, the two tables (12 B per ray, at least one ray), and the job storage of one launch round, which shades at
+ * most 4 samples per pixel: 4 x (36 B, or 52 B with Phong) per pixel. */
+cvr_status  cvr_crtgt_begin(cvr_ctx* ctx, const cvr_frame* frame, const cvr_crtgt_params* params,
+                            const float* occ_rays, int n_occ, const float* sdw_rays, int n_sdw);
+/* Extends every unfinished ray by at most max_samples (>= 1) loop iterations, in
+ * launch rounds of at most 4 iterations per pixel (the bound of the job storage),
+ * and stops early once every pixel is done.  Writes the current image and counts to
+ * `out` (NULL: no copy; host or device pointers, either format; total: the sum of the
+ * counts so far -- added to a device total, as every renderer does).  Reports the
+ * pixels still unfinished; 0 = converged, after which the call only copies.  Blocks
+ * until the rounds are done.  CVR_ERR_STATE without a cvr_crtgt_begin, and after a
+ * new volume, transfer function or gradient. */
+cvr_status  cvr_crtgt_advance(cvr_ctx* ctx, int max_samples, const cvr_output* out,
+                              unsigned long long* unfinished_pixels);
+/* cvr_crtgt_begin, then cvr_crtgt_advance until converged. */
+cvr_status  cvr_render_crtgt(cvr_ctx* ctx, const cvr_frame* frame, const cvr_crtgt_params* params,
+                             const float* occ_rays, int n_occ, const float* sdw_rays, int n_sdw,
+                             const cvr_output* out);
 
 /* The reference renderers' default parameters for `variant`. */
 void        cvr_iso_params_default(int variant, cvr_iso_params* out);

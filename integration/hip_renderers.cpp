@@ -167,6 +167,102 @@ cvr_status HipDirOcclusionShading::RenderFrame (const cvr_output* out)
 }
 
 ////////////////////////////////////////////////////////////////////////////////
+// RC1PConeLightGroundTruthSteps (crtgtrenderer.cpp:23-325)
+////////////////////////////////////////////////////////////////////////////////
+HipRC1PConeLightGroundTruthSteps::HipRC1PConeLightGroundTruthSteps ()
+  : HipRendererBase(0)
+  , m_frame_outdated(true)
+  , m_u_step_size(0.5f)
+  , m_apply_gradient(false)
+  , m_u_light_ray_initial_step(1.0f)
+  , m_u_light_ray_step_size(0.5f)
+  , m_light_parameters_outdated(true)
+  , m_apply_occlusion(false)
+  , m_occ_num_rays_sampled(1)
+  , m_occ_cone_aperture_angle(90.f)
+  , m_occ_cone_distance_eval(100.0f)
+  , m_apply_shadows(false)
+  , m_sdw_num_rays_sampled(1)
+  , m_sdw_cone_aperture_angle(1.0f)
+  , m_sdw_cone_distance_eval(100.0f)
+  , m_shadow_type(0)
+  , samples_per_redraw(1)
+  , ray_seed(1)
+  , m_params()
+{
+}
+
+bool HipRC1PConeLightGroundTruthSteps::Init (int swidth, int sheight)
+{
+  if (IsBuilt()) Clean();
+  if (m_ext_data_manager->GetCurrentVolumeTexture() == nullptr) return false;   // :98
+  if (!UploadVolume() || !UploadTransferFunction() || !UploadGradient(m_apply_gradient))
+    return false;
+  m_u_step_size = DefaultStep();                                                // :107-108
+  vis::StructuredGridVolume* vol = m_ext_data_manager->GetCurrentStructuredVolume();
+  m_occ_cone_distance_eval = (float)(vol->GetDiagonal() * 0.50f);               // :112-113
+  m_sdw_cone_distance_eval = (float)(vol->GetDiagonal() * 0.75f);
+  Reshape(swidth, sheight);
+  SetBuilt(true);
+  SetOutdated();
+  return true;
+}
+
+// Update (:121-260): new ray tables when a count or an aperture changed, the
+// uniforms, and a frame that starts over.
+bool HipRC1PConeLightGroundTruthSteps::Update (vis::Camera* camera)
+{
+  vis::RenderingParameters* rp = m_ext_rendering_parameters;
+  FillFrame(camera);
+  if (m_light_parameters_outdated)
+  {
+    m_occ_rays.assign((size_t)(m_occ_num_rays_sampled > 0 ? m_occ_num_rays_sampled : 0) * 3, 0.0f);
+    m_sdw_rays.assign((size_t)(m_sdw_num_rays_sampled > 0 ? m_sdw_num_rays_sampled : 0) * 3, 0.0f);
+    if (cvr_crtgt_build_rays(m_occ_cone_aperture_angle, (int)(m_occ_rays.size() / 3),
+                             m_sdw_cone_aperture_angle, (int)(m_sdw_rays.size() / 3), ray_seed,
+                             m_occ_rays.empty() ? nullptr : m_occ_rays.data(),
+                             m_sdw_rays.empty() ? nullptr : m_sdw_rays.data()) != CVR_OK)
+      return Fail("cvr_crtgt_build_rays");
+    m_light_parameters_outdated = false;
+  }
+  cvr_crtgt_params_default(&m_params);
+  m_params.step = m_u_step_size;
+  m_params.apply_gradient_shading =
+      (m_apply_gradient && m_ext_data_manager->GetCurrentGradientTexture()) ? 1 : 0;
+  m_params.ka = rp->GetBlinnPhongKambient();
+  m_params.kd = rp->GetBlinnPhongKdiffuse();
+  m_params.ks = rp->GetBlinnPhongKspecular();
+  m_params.shininess = rp->GetBlinnPhongNshininess();
+  copy3(m_params.light.position, rp->GetBlinnPhongLightingPosition());
+  copy3(m_params.light.forward, rp->GetBlinnPhongLightSourceCameraForward());
+  copy3(m_params.light.up, rp->GetBlinnPhongLightSourceCameraUp());
+  copy3(m_params.light.right, rp->GetBlinnPhongLightSourceCameraRight());
+  m_params.light.spot_angle_deg = rp->GetSpotLightMaxAngle();
+  m_params.light_gap = m_u_light_ray_initial_step;
+  m_params.light_step = m_u_light_ray_step_size;
+  m_params.apply_occlusion = m_apply_occlusion ? 1 : 0;
+  m_params.occ_distance = m_occ_cone_distance_eval;
+  m_params.apply_shadow = m_apply_shadows ? 1 : 0;
+  m_params.sdw_distance = m_sdw_cone_distance_eval;
+  m_params.shadow_type = m_shadow_type;
+  m_frame_outdated = true;
+  if (cvr_crtgt_begin(m_cvr, &frame_, &m_params, m_occ_rays.data(), (int)(m_occ_rays.size() / 3),
+                      m_sdw_rays.data(), (int)(m_sdw_rays.size() / 3)) != CVR_OK)
+    return Fail("cvr_crtgt_begin");
+  return true;
+}
+
+// RedrawFrameTexture (:272-325): one more dispatch while a pixel is unfinished; a
+// ready frame is only copied.
+cvr_status HipRC1PConeLightGroundTruthSteps::RenderFrame (const cvr_output* out)
+{
+  unsigned long long left = 0;
+  const cvr_status st = cvr_crtgt_advance(m_cvr, samples_per_redraw > 0 ? samples_per_redraw : 1, out, &left);
+  if (st == CVR_OK) m_frame_outdated = left > 0;
+  return st;
+}
+
+////////////////////////////////////////////////////////////////////////////////
 // RC1PExtinctionBasedShading (ebsrenderer.cpp:18-260, 624-723)
 ////////////////////////////////////////////////////////////////////////////////
 HipExtinctionBasedShading::HipExtinctionBasedShading ()

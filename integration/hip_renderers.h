@@ -7,6 +7,8 @@
  *                                                              (rc1pdosct/dosrcrenderer.h:40-120)
  *   HipExtinctionBasedShading        <- RC1PExtinctionBasedShading
  *                                                              (rc1pextbsd/ebsrenderer.h:47-123)
+ *   HipRC1PConeLightGroundTruthSteps <- RC1PConeLightGroundTruthSteps
+ *                                                              (rc1pcrtgt/crtgtrenderer.h:50-118)
  *   HipRayCasting1PassIsoAdapt       <- RayCasting1PassIsoAdapt (rc1pisoadapt/rc1pisoadaptrenderer.h)
  *   HipCustomRayCasting1PassIsoAdapt <- CustomRayCasting1PassIsoAdapt (rc1pisocustom/...)
  *   HipCustomRayCasting1PassIsodfsAdapt <- CustomRayCasting1PassIsodfsAdapt (rc1pisodfscustom/...)
@@ -106,6 +108,46 @@ protected:
   cvr_status RenderFrame (const cvr_output* out) override;
   bool UploadExtinctionSAT ();         // GenerateExtinctionSAT3DTex (:624-723), on the GPU
   cvr_ebs_params m_params;
+};
+
+// The ground truth of the two renderers above: every sample shaded by secondary rays
+// cast through the volume.  Progressive, as the reference: Update resets the frame
+// (cvr_crtgt_begin) and every Redraw extends each unfinished ray by
+// samples_per_redraw iterations (the reference: one) until the frame is ready; the
+// state lives in the library, in float (DESIGN.md 5d').  One GPU: the library's group
+// contexts refuse these calls.
+class HipRC1PConeLightGroundTruthSteps : public HipRendererBase
+{
+public:
+  HipRC1PConeLightGroundTruthSteps ();
+  const char* GetName () override { return "1-Pass - Ray Casting - Cone Ground Truth (Steps) (HIP, MI355X)"; }
+  const char* GetAbbreviationName () override { return "s_1rc_gt_c_hip"; }
+  bool Init (int shader_width, int shader_height) override;
+  bool Update (vis::Camera* camera) override;
+
+  // crtgtrenderer.cpp:23-51
+  bool m_frame_outdated;
+  float m_u_step_size;
+  bool m_apply_gradient;
+  float m_u_light_ray_initial_step;
+  float m_u_light_ray_step_size;
+  bool m_light_parameters_outdated;
+  bool m_apply_occlusion;
+  int m_occ_num_rays_sampled;
+  float m_occ_cone_aperture_angle;
+  float m_occ_cone_distance_eval;
+  bool m_apply_shadows;
+  int m_sdw_num_rays_sampled;
+  float m_sdw_cone_aperture_angle;
+  float m_sdw_cone_distance_eval;
+  int m_shadow_type;                   // 0 point, 1 spot, 2 directional
+  int samples_per_redraw;              // iterations per pixel and Redraw (>= 1)
+  unsigned ray_seed;                   // the tables' generator (cvr_crtgt_build_rays)
+
+protected:
+  cvr_status RenderFrame (const cvr_output* out) override;
+  cvr_crtgt_params m_params;
+  std::vector<float> m_occ_rays, m_sdw_rays;
 };
 
 // The three single-pass isosurface ray-casters share one library entry point
