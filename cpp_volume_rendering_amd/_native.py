@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = (
     "cvr_compute_light_cache_extbsd", "cvr_render_extbsd_preillum",
     "cvr_crtgt_params_default", "cvr_crtgt_build_rays", "cvr_crtgt_begin", "cvr_crtgt_advance",
     "cvr_render_crtgt",
+    "cvr_vct_params_default", "cvr_tf1d_opacity_lut", "cvr_vct_set_opacity", "cvr_vct_precompute",
+    "cvr_vct_info", "cvr_vct_read_pyramid", "cvr_vct_read_table", "cvr_render_vct",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
     "cvr_decode_tiles", "cvr_comm_init_local", "cvr_create_group", "cvr_group_size",
@@ -143,6 +145,26 @@ class CrtgtParams(ctypes.Structure):
                 ("apply_occlusion", ctypes.c_int), ("occ_distance", ctypes.c_float),
                 ("apply_shadow", ctypes.c_int), ("sdw_distance", ctypes.c_float),
                 ("shadow_type", ctypes.c_int)]
+
+
+VCT_MAX_LEVELS, VCT_MAX_SAMPLES, VCT_TABLE_WIDTH = 16, 10000, 255   # cvr.h CVR_VCT_*
+
+
+class VctParams(ctypes.Structure):
+    _fields_ = [("step", ctypes.c_float), ("apply_gradient_shading", ctypes.c_int),
+                ("ka", ctypes.c_float), ("kd", ctypes.c_float), ("ks", ctypes.c_float),
+                ("shininess", ctypes.c_float), ("ispecular", ctypes.c_float * 3), ("light", Light),
+                ("apply_occlusion", ctypes.c_int), ("apply_shadow", ctypes.c_int),
+                ("cone_step", ctypes.c_float), ("cone_step_increase_rate", ctypes.c_float),
+                ("cone_initial_step", ctypes.c_float), ("cone_apex_angle_deg", ctypes.c_float),
+                ("apply_correction", ctypes.c_int), ("correction_factor", ctypes.c_float),
+                ("samples", ctypes.c_int)]
+
+
+class VctPyramidInfo(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int), ("dims", (ctypes.c_int * 3) * VCT_MAX_LEVELS),
+                ("max_stddev", ctypes.c_double), ("table_width", ctypes.c_int),
+                ("table_height", ctypes.c_int)]
 
 
 class IsoParams(ctypes.Structure):
@@ -259,6 +281,15 @@ def lib() -> ctypes.CDLL:
         "cvr_crtgt_advance": ([P, I, ctypes.POINTER(Output), ctypes.POINTER(ctypes.c_ulonglong)], I),
         "cvr_render_crtgt": ([P, ctypes.POINTER(Frame), ctypes.POINTER(CrtgtParams), FP, I, FP, I,
                               ctypes.POINTER(Output)], I),
+        "cvr_vct_params_default": ([ctypes.POINTER(VctParams)], None),
+        "cvr_tf1d_opacity_lut": ([DP, I, DP, I, I, I, FP], I),
+        "cvr_vct_set_opacity": ([P, FP, I], I),
+        "cvr_vct_precompute": ([P], I),
+        "cvr_vct_info": ([P, ctypes.POINTER(VctPyramidInfo)], I),
+        "cvr_vct_read_pyramid": ([P, I, FP], I),
+        "cvr_vct_read_table": ([P, FP], I),
+        "cvr_render_vct": ([P, ctypes.POINTER(Frame), ctypes.POINTER(VctParams),
+                            ctypes.POINTER(Output)], I),
         "cvr_iso_params_default": ([I, ctypes.POINTER(IsoParams)], None),
         "cvr_render_iso": ([P, ctypes.POINTER(Frame), ctypes.POINTER(IsoParams),
                             ctypes.POINTER(Output)], I),

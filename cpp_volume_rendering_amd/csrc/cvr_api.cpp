@@ -118,6 +118,7 @@ static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, in
   c->cone_valid = 0;
   light_cache_drop(c);
   crtgt_invalidate(c);
+  vct_drop(c, true);
   HIP_TRY(c, hipMalloc((void**)&c->d_lut, nv * sizeof(uint16_t)));
   uint16_t* d_lut = c->d_lut;
   hipError_t e = hipMemcpyAsync(d_lut, lut.data(), nv * sizeof(uint16_t), hipMemcpyHostToDevice,
@@ -198,6 +199,24 @@ cvr_status cvr_tf1d_build_rgbt(const double* rgb_cp, int n_rgb, const double* a_
     float v4 = (float)tab[(size_t)i * 4 + 3];
     if (!extinction_input) v4 = (float)std::log(1.0 / (1.0 - (double)v4));
     out_rgbt[i * 4 + 3] = v4;
+  }
+  return CVR_OK;
+}
+
+// TransferFunction1D::GetOpc(i, max_density) = Get(i, max_density).a for integer i
+// below max_density (transferfunction1d.cpp:132-167): value = i * (max / max), the
+// interpolation weight t = 0, so (float)((1 - 0) * tab[i] + 0 * tab[i + 1]).
+cvr_status cvr_tf1d_opacity_lut(const double* rgb_cp, int n_rgb, const double* a_cp, int n_a,
+                                int max_density, int n, float* out_opacity) {
+  if (!out_opacity || n != CVR_VCT_TABLE_WIDTH || max_density < n) return CVR_ERR_ARG;
+  std::vector<double> tab;
+  cvr_status st = build_tf_table(rgb_cp, n_rgb, a_cp, n_a, max_density, tab);
+  if (st != CVR_OK) return st;
+  for (int i = 0; i < n; i++) {
+    const double value = (double)i * ((double)max_density / (double)max_density);
+    const int iv = (int)value;
+    const double t = value - iv;
+    out_opacity[i] = (float)((1.0 - t) * tab[(size_t)iv * 4 + 3] + t * tab[(size_t)(iv + 1) * 4 + 3]);
   }
   return CVR_OK;
 }
@@ -284,6 +303,7 @@ void cvr_destroy(cvr_ctx* ctx) {
   delete[] c->cone_tab;
   light_cache_drop(c);
   crtgt_release(c);
+  vct_drop(c, true);
   if (c->lc_ev) (void)hipEventDestroy(c->lc_ev);
   free_dev(c->d_total);
   free_dev(c->d_scratch);
@@ -341,7 +361,7 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
     return b;
   }
   return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
-         c->lc_bytes + c->gt.bytes;
+         c->lc_bytes + c->gt.bytes + c->vct.bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {
@@ -388,6 +408,7 @@ cvr_status cvr_set_transfer_function(cvr_ctx* ctx, const float* rgbt, int n) {
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
   light_cache_drop(c);
   crtgt_invalidate(c);
+  vct_drop(c, false);
   if (n != c->tf_n) {
     free_dev(c->d_tf);
     HIP_TRY(c, hipMalloc((void**)&c->d_tf, (size_t)n * 16));

@@ -117,6 +117,10 @@ void light_cache_drop(Ctx* c);
 void crtgt_invalidate(Ctx* c);
 void crtgt_release(Ctx* c);
 
+// cvr_vct.cpp: a new volume drops the pyramid and the table, a new TF the table
+// and the opacities; the context's end frees everything
+void vct_drop(Ctx* c, bool pyramid);
+
 // cvr_dos.cpp, cvr_ebs.cpp: a frame's kernel arguments (also for the light cache)
 void resolve_cone_params(const Ctx* c, const cvr_dos_params* p, cvr_cone_params cp[2]);
 cvr_status dos_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_dos_params* p,

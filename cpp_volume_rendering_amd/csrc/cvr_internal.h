@@ -206,6 +206,41 @@ struct CrtgtState {
   unsigned long long* ctr = nullptr; // [0] jobs of the round, [1] unfinished pixels, [2] iterations so far
 };
 
+// Voxel cone tracing (vct.hip, vct_precompute.hip).  The pyramid is RG16F, one
+// uint32 per texel (mean in the low half, standard deviation in the high half),
+// x fastest, the levels concatenated.
+constexpr int kMaxVctLevels = CVR_VCT_MAX_LEVELS;
+struct VctLevel {                    // one level as the cone fetches address it
+  int off;                           // first texel of the level
+  int d[3];                          // dimensions
+  float s[3];                        // d / G: texel coordinate = fma(p, d / G, -0.5)
+  float m[3];                        // d - 1 (clamp-to-edge bound)
+};
+// One sample of the cone schedule (wave-uniform: it depends on the cone parameters
+// only, so one thread computes all of it once, vct.hip vct_schedule_kernel)
+struct VctStep {
+  float xl;                          // apex_distance + step_size / 2
+  float expo;                        // step_size * corr_fact
+  float frac;                        // the level fraction (filter_weight applied); 0 with one level
+  int nlev;                          // 1: lv[0] only, 2: lerp(lv[0], lv[1], frac)
+  VctLevel lv[2];
+};
+struct VctArgs {
+  Rc1passArgs a;                     // ray, volume, TF, Blinn-Phong constants, tiles
+  float G[3];                        // VolumeScaledSizes
+  int apply_shadow, phong;
+  float ka, kd, ks;                  // Kambient if occlusion, Kdiffuse / Kspecular if shadow, else 0
+  int samples;                       // ConeNumberOfSamples
+  float tab_w, tab_h;                // table dimensions as float (texel coordinate = fma(u, n, -0.5))
+  float max_density, max_stddev;     // VolumeMaxDensity (255), (float)VolumeMaxStandardDeviation
+  int tab_wi, tab_hi;
+};
+struct VctData {
+  const uint32_t* pyr;               // the pyramid
+  const uint16_t* table;             // R16F, tab_hi rows of tab_wi
+  const VctStep* steps;              // [samples]
+};
+
 // Isosurface ray-casters with block skipping (iso.hip): the shaders' uniforms.
 struct IsoArgs {
   Rc1passArgs a;                     // ray, volume, Blinn-Phong constants, tiles
@@ -457,6 +492,26 @@ struct Ctx {
     int ntiles = 0;
     unsigned long long unfinished = 0;
   } gt;
+  // voxel cone tracing (cvr_vct.cpp): the supervoxel pyramid of the volume, the
+  // pre-integration table of (volume, opacities) and the cone schedule of the
+  // last frame's parameters
+  struct Vct {
+    uint32_t* d_pyr = nullptr;
+    VctLevel* d_levels = nullptr;      // [kMaxVctLevels]
+    VctLevel levels[kMaxVctLevels] = {};
+    int nl = 0;                        // 0: no pyramid
+    size_t texels = 0;
+    double max_stddev = 0.0;
+    int builds = 0;                    // option "vct_pyramid_builds" (read-only)
+    std::vector<float> opacity;        // GetOpc(i, 255), i < 255; empty: not set
+    uint16_t* d_table = nullptr;
+    int tab_h = 0;                     // 0: no table
+    VctStep* d_steps = nullptr;
+    int steps_cap = 0;
+    float steps_key[8] = {};           // what d_steps was computed from
+    int steps_valid = 0;
+    size_t bytes = 0;                  // all of the above (cvr_device_bytes)
+  } vct;
   unsigned long long* d_tile_samples = nullptr;   // per-wave-tile sample counts (zeroed)
   int tile_samples_n = 0;
   // d_tile_samples and d_shade are one set per context: a frame that uses them on
@@ -558,6 +613,17 @@ hipError_t launch_crtgt_init(const CrtgtArgs& q, const CrtgtState& st, hipStream
 hipError_t launch_crtgt_round(const Ctx& c, const CrtgtArgs& q, const CrtgtState& st, int k, hipStream_t s);
 hipError_t launch_crtgt_store(const CrtgtArgs& q, const CrtgtState& st, float4* out, uint32_t* samples,
                               unsigned long long* total, int half, hipStream_t s);
+// vct_precompute.hip: the pyramid of the context's u8 volume (levels laid out by
+// `lv`; scratch: doubles for the means of every level >= 1; max_bits: the largest
+// standard deviation's double bits, zeroed by the caller)
+hipError_t launch_vct_pyramid(const Ctx& c, const VctLevel* lv, int nl, uint32_t* pyr, double* scratch,
+                              unsigned long long* max_bits, hipStream_t s);
+// vct.hip: the cone schedule of a frame's parameters, and the frame
+hipError_t launch_vct_schedule(const VctLevel* d_levels, int nl, float initial, float step, float rate,
+                               float tan_apex, float corr, int n, int filter_bits, VctStep* out,
+                               hipStream_t s);
+hipError_t launch_vct(const Ctx& c, const VctArgs& q, const VctData& data, float4* out, uint32_t* samples,
+                      unsigned long long* shade, unsigned long long* tile_samples, hipStream_t s);
 // iso.hip: raw per-block extremes (uint2), and the isosurface march (variant 0/1)
 hipError_t launch_block_minmax(const void* vox, int bpv, const int N[3], const int nb[3], uint2* out,
                                hipStream_t s);

@@ -150,6 +150,7 @@ const Option kOptions[] = {
      },
      1, 0, nullptr, nullptr, nullptr},
     {"light_cache_builds", &Ctx::lc_builds, nullptr, 1, 0, nullptr, nullptr, nullptr},
+    {"vct_pyramid_builds", nullptr, [](const Ctx* c) { return c->vct.builds; }, 1, 0, nullptr, nullptr, nullptr},
 };
 
 const Option* find_option(const char* key) {

@@ -99,6 +99,7 @@ class DataManager:
         self.tf_rgbt: Optional[np.ndarray] = None  # (n, 4) float32: r, g, b, extinction
         self.tf_rgba: Optional[np.ndarray] = None  # (n, 4) float32: r, g, b, opacity
         self.ext_lut: Optional[np.ndarray] = None  # GetExtN per voxel value (EBS SAT cells)
+        self.opacity_lut: Optional[np.ndarray] = None  # GetOpc(i, 255), i < 255 (VCT table)
         self.gradient_type = N.GRADIENT_NONE        # datamanager.cpp:27 (NONE by default)
         self.name = ""
 
@@ -156,6 +157,10 @@ class DataManager:
         """GetExtN(v / (2^bits - 1)) for every voxel value (build_ext_lut)."""
         self.ext_lut = np.ascontiguousarray(ext_lut, dtype=np.float32)
 
+    def SetOpacityTable(self, opacity_lut: np.ndarray):
+        """GetOpc(i, 255) for i < 255 (build_opacity_lut)."""
+        self.opacity_lut = np.ascontiguousarray(opacity_lut, dtype=np.float32)
+
     def ReadTransferFunction(self, path: str):
         self.SetTransferFunction(read_tf1d(path))
 
@@ -185,6 +190,17 @@ def build_ext_lut(rgb_cp, alpha_cp, bytes_per_voxel: int = 1, max_density: int =
     N.check(N.lib().cvr_tf1d_ext_lut(N.dptr(rgb), rgb.shape[0], N.dptr(a), a.shape[0],
                                      max_density, int(extinction_input), int(bytes_per_voxel),
                                      N.fptr(out)), "cvr_tf1d_ext_lut")
+    return out
+
+
+def build_opacity_lut(rgb_cp, alpha_cp, max_density: int = 255) -> np.ndarray:
+    """TransferFunction1D::GetOpc(i, 255) for i < 255: what the voxel cone tracing renderer's
+    pre-integration table integrates."""
+    rgb = np.ascontiguousarray(np.asarray(rgb_cp, dtype=np.float64).reshape(-1, 4))
+    a = np.ascontiguousarray(np.asarray(alpha_cp, dtype=np.float64).reshape(-1, 2))
+    out = np.empty(N.VCT_TABLE_WIDTH, dtype=np.float32)
+    N.check(N.lib().cvr_tf1d_opacity_lut(N.dptr(rgb), rgb.shape[0], N.dptr(a), a.shape[0],
+                                         max_density, out.shape[0], N.fptr(out)), "cvr_tf1d_opacity_lut")
     return out
 
 
@@ -304,6 +320,39 @@ class Device:
         t = np.ascontiguousarray(ext_lut, dtype=np.float32)
         N.check(N.lib().cvr_set_extinction_sat(self.handle, N.fptr(t), t.shape[0]),
                 "cvr_set_extinction_sat", self.handle)
+
+    def vct_set_opacity(self, opacity: np.ndarray):
+        """GetOpc(i, 255), i < 255, of the current TF (build_opacity_lut)."""
+        t = np.ascontiguousarray(opacity, dtype=np.float32)
+        N.check(N.lib().cvr_vct_set_opacity(self.handle, N.fptr(t), t.shape[0]), "cvr_vct_set_opacity",
+                self.handle)
+
+    def vct_precompute(self):
+        N.check(N.lib().cvr_vct_precompute(self.handle), "cvr_vct_precompute", self.handle)
+
+    def vct_info(self) -> N.VctPyramidInfo:
+        info = N.VctPyramidInfo()
+        N.check(N.lib().cvr_vct_info(self.handle, ctypes.byref(info)), "cvr_vct_info", self.handle)
+        return info
+
+    def vct_pyramid(self) -> list:
+        """The supervoxel pyramid: level i as a (d, h, w, 2) float32 array of (mean, stddev)."""
+        info = self.vct_info()
+        out = []
+        for l in range(info.levels):
+            w, h, d = (int(v) for v in info.dims[l])
+            a = np.zeros((d, h, w, 2), np.float32)
+            N.check(N.lib().cvr_vct_read_pyramid(self.handle, l, N.fptr(a)), "cvr_vct_read_pyramid",
+                    self.handle)
+            out.append(a)
+        return out
+
+    def vct_table(self) -> np.ndarray:
+        """The pre-integration table, (table_height, 255) float32."""
+        info = self.vct_info()
+        a = np.zeros((info.table_height, info.table_width), np.float32)
+        N.check(N.lib().cvr_vct_read_table(self.handle, N.fptr(a)), "cvr_vct_read_table", self.handle)
+        return a
 
     def extinction_sat(self) -> np.ndarray:
         """The float SAT as a (D+2, H+2, W+2) array."""
@@ -818,6 +867,68 @@ class RC1PExtinctionBasedShading(RayCasting1Pass):
                                                    ctypes.byref(self._params), dims,
                                                    ctypes.byref(out)),
                 "cvr_render_extbsd_preillum", self.device.handle)
+
+
+class RC1PVoxelConeTracingSGPU(RayCasting1Pass):
+    """HIP implementation of RC1PVoxelConeTracingSGPU
+    (cppvolrend/structured/rc1pvctsg/vctrenderer.cpp): the single-pass march with one voxel
+    cone toward the light per sample, through the supervoxel pyramid and the pre-integration
+    table (image-space mode; the light-cache mode is not built)."""
+
+    def __init__(self, device: int = 0, devices=None):
+        super().__init__(device, devices)
+        self.apply_ambient_occlusion = True          # vctrenderer.cpp:33-43
+        self.apply_voxel_cone_tracing = True
+        self.cone_step_size = 2.0
+        self.cone_step_size_increase_rate = 1.0
+        self.cone_initial_step = 2.0
+        self.cone_apex_angle = 2.0
+        self.apply_correction_factor = True
+        self.opacity_correction_factor = 2.0
+        self.cone_number_of_samples = 50
+        self.covered_distance = 0.0
+        self._params = N.VctParams()
+
+    def GetName(self): return "1-Pass - Ray Casting - Voxel Cone Tracing"
+    def GetAbbreviationName(self): return "s_1rc_vct"
+
+    def Init(self, swidth: int, sheight: int) -> bool:
+        dm = self.m_ext_data_manager
+        if dm is None or dm.opacity_lut is None:
+            return False
+        if not super().Init(swidth, sheight):        # m_u_step_size from the default step (:114-115)
+            return False
+        self.device.vct_set_opacity(dm.opacity_lut)
+        self.device.vct_precompute()                 # PreProcessSuperVoxels / PreIntegrationTable (:94-95)
+        return True
+
+    def Update(self, camera: Camera) -> bool:
+        rp = self.m_ext_rendering_parameters or RenderingParameters()
+        self._frame = self._camera_frame(camera)
+        p = self._params
+        p.step = float(self.m_u_step_size)
+        p.apply_gradient_shading = int(bool(self.m_apply_gradient_shading) and
+                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
+        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
+        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
+        p.ispecular[:] = [float(v) for v in rp.light_specular]
+        p.light.position[:] = [float(v) for v in rp.light_position]
+        p.light.forward[:] = [float(v) for v in rp.light_forward]
+        p.light.up[:] = [float(v) for v in rp.light_up]
+        p.light.right[:] = [float(v) for v in rp.light_right]
+        p.light.spot_angle_deg = float(rp.spot_light_angle)
+        p.apply_occlusion = int(bool(self.apply_ambient_occlusion))
+        p.apply_shadow = int(bool(self.apply_voxel_cone_tracing))
+        p.cone_step = float(self.cone_step_size)
+        p.cone_step_increase_rate = float(self.cone_step_size_increase_rate)
+        p.cone_initial_step = float(self.cone_initial_step)
+        p.cone_apex_angle_deg = float(self.cone_apex_angle)
+        p.apply_correction = int(bool(self.apply_correction_factor))
+        p.correction_factor = float(self.opacity_correction_factor)
+        p.samples = int(self.cone_number_of_samples)
+        return True
+
+    _ENTRY = "cvr_render_vct"
 
 
 def build_crtgt_rays(occ_aperture_deg: float, n_occ: int, sdw_aperture_deg: float, n_sdw: int,

@@ -46,6 +46,11 @@
  *                                   _common_shaders/obj_ray_marching.comp
  *   cvr_crtgt_begin / _advance   <- RC1PConeLightGroundTruthSteps::Update + RedrawFrameTexture
  *   cvr_render_crtgt                cppvolrend/structured/rc1pcrtgt/crtgtrenderer.cpp:121-325
+ *   cvr_vct_precompute           <- VCTPreProcessing::PreProcessSuperVoxels + PreProcessPreIntegrationTable
+ *                                   cppvolrend/structured/rc1pvctsg/preprocessingstages.cpp:35-202
+ *   cvr_render_vct               <- RC1PVoxelConeTracingSGPU::Update + Redraw
+ *                                   cppvolrend/structured/rc1pvctsg/vctrenderer.cpp:124-250
+ *                                   (the dispatch of vct_ray_bbox_marching.comp)
  *                                   (the dispatches of gt_ray_marching.comp, one sample per
  *                                   pixel each, until every pixel's state says "done")
  *   cvr_crtgt_build_rays         <- the ray tables of Update, crtgtrenderer.cpp:131-184
@@ -635,6 +640,91 @@ cvr_status  cvr_crtgt_advance(cvr_ctx* ctx, int max_samples, const cvr_output* o
 cvr_status  cvr_render_crtgt(cvr_ctx* ctx, const cvr_frame* frame, const cvr_crtgt_params* params,
                              const float* occ_rays, int n_occ, const float* sdw_rays, int n_sdw,
                              const cvr_output* out);
+
+/* ----------------------------------------------------------------------------
+ * Voxel cone tracing (RC1PVoxelConeTracingSGPU, "1-Pass - Ray Casting - Voxel Cone
+ * Tracing", s_1rc_vct: rc1pvctsg/vctrenderer.cpp, preprocessingstages.cpp,
+ * vct_ray_bbox_marching.comp).  The march of cvr_render_rc1pass with every sample
+ * of alpha > 0 shaded by one cone toward the light (:97-144): up to `samples`
+ * quadrilinear fetches of a (mean, standard deviation) supervoxel pyramid of the
+ * volume, each mapped to an opacity by a 2-D pre-integration table of the transfer
+ * function, the transmittances multiplied.  ShadeSample (:146-189) has no occlusion
+ * term: ka is Kambient with apply_occlusion on, kd / ks are nonzero with
+ * apply_shadow on, and with both off the colour is 0 * (1 / 0) = NaN, as written.
+ * corr_fact is apply_correction * correction_factor, so with the correction off the
+ * exponent is 0 and every shadow vanishes (pow(x, 0) = 1, also for x = 0), as written.
+ *
+ * Scope: 1-byte volumes only (the reference scales the mean by a hard-coded 255 but
+ * normalises 16-bit data by 65535: a 2-byte volume returns CVR_ERR_ARG).  A volume
+ * whose maximum standard deviation is 0 (constant over every 2x2x2 block of every
+ * level) gives a table of height 0 and returns CVR_ERR_ARG.  A mipmap level at or
+ * above the last computed one reads the last level only (the reference uploads no
+ * level beyond it).  The object-space light-cache mode (lightcachecomputation.comp)
+ * is not built.  Honours filter_bits; with native_exp set the calls return
+ * CVR_ERR_ARG.
+ *
+ * The pyramid depends on the volume only; the table on the volume (its height) and
+ * on the opacities of cvr_vct_set_opacity.  cvr_set_volume drops both;
+ * cvr_set_transfer_function drops the table and the opacities (they belong to the
+ * old TF), so the next frame needs a new cvr_vct_set_opacity and rebuilds only the
+ * table.  Device memory, counted by cvr_device_bytes once built: 4 B per texel of
+ * every pyramid level (level i has floor(dim / 2^i) texels per axis), 640 B of level
+ * addressing, 2 B x 255 x ceil(max_stddev) of table, and 96 B per cone sample of the
+ * last frame's cone schedule (at least one sample).
+ * -------------------------------------------------------------------------- */
+#define CVR_VCT_MAX_LEVELS 16
+#define CVR_VCT_MAX_SAMPLES 10000     /* the reference UI's bound                      */
+#define CVR_VCT_TABLE_WIDTH 255       /* ceil(GetMaxDensity()) of a 1-byte volume      */
+typedef struct cvr_vct_params {
+  float step;                  /* <= 0: 0.5/sqrt(3)*|scale| (vctrenderer.cpp:114-115)   */
+  int   apply_gradient_shading;/* m_apply_gradient_shading (needs cvr_set_gradient)     */
+  float ka, kd, ks, shininess; /* Blinn-Phong constants (renderingparameters.cpp:23-26) */
+  float ispecular[3];          /* Ispecular                                             */
+  cvr_light light;             /* the current light source (its position is read)       */
+  int   apply_occlusion;       /* apply_ambient_occlusion (default 1)                   */
+  int   apply_shadow;          /* apply_voxel_cone_tracing (default 1)                  */
+  float cone_step;             /* cone_step_size (2.0, world units, > 0)                */
+  float cone_step_increase_rate; /* cone_step_size_increase_rate (1.0, >= 1)            */
+  float cone_initial_step;     /* cone_initial_step (2.0)                               */
+  float cone_apex_angle_deg;   /* cone_apex_angle (2.0, in (0, 90))                     */
+  int   apply_correction;      /* apply_correction_factor (default 1)                   */
+  float correction_factor;     /* opacity_correction_factor (2.0)                       */
+  int   samples;               /* cone_number_of_samples (50, in [0, CVR_VCT_MAX_SAMPLES]) */
+} cvr_vct_params;
+/* The reference's defaults (vctrenderer.cpp:33-43): step 0 (the default step), no
+ * Phong, (0.5, 0.5, 0.8, 30), white specular, light 0 of the reference's light list. */
+void        cvr_vct_params_default(cvr_vct_params* out);
+typedef struct cvr_vct_pyramid_info {
+  int    levels;                          /* 0: not built                              */
+  int    dims[CVR_VCT_MAX_LEVELS][3];
+  double max_stddev;                      /* maximum_standard_deviation                */
+  int    table_width, table_height;       /* 255 x ceil(max_stddev); height 0: no table */
+} cvr_vct_pyramid_info;
+/* TransferFunction1D::GetOpc(i, 255) for i = 0 .. 254 (transferfunction1d.cpp:132-167),
+ * the opacities the pre-integration table integrates, from the control points of
+ * cvr_tf1d_build_rgbt.  n must be CVR_VCT_TABLE_WIDTH.  Touches no device. */
+cvr_status  cvr_tf1d_opacity_lut(const double* rgb_cp, int n_rgb, const double* a_cp, int n_a,
+                                 int max_density, int n, float* out_opacity);
+/* The opacities of the current transfer function (n = CVR_VCT_TABLE_WIDTH); drops
+ * the table. */
+cvr_status  cvr_vct_set_opacity(cvr_ctx* ctx, const float* opacity, int n);
+/* Builds what is stale: the pyramid (PreProcessSuperVoxels, preprocessingstages.cpp
+ * :35-145, on the GPU in double) and, when the opacities are set, the table
+ * (PreProcessPreIntegrationTable, :147-202, on the host in double).  Idempotent.
+ * Option "vct_pyramid_builds" (read-only) counts the pyramid builds. */
+cvr_status  cvr_vct_precompute(cvr_ctx* ctx);
+cvr_status  cvr_vct_info(cvr_ctx* ctx, cvr_vct_pyramid_info* out);
+/* Level `level` as w*h*d (mean, stddev) pairs, x fastest, and the table as
+ * table_height rows of 255: the stored binary16 values widened to float. */
+cvr_status  cvr_vct_read_pyramid(cvr_ctx* ctx, int level, float* out_rg);
+cvr_status  cvr_vct_read_table(cvr_ctx* ctx, float* out);
+/* One frame; builds whatever is stale first.  Screen tiles (cvr_frame rank / nranks)
+ * and group contexts as cvr_render_dosct.  CVR_ERR_STATE without a volume, a TF, the
+ * opacities, or (with Phong) a gradient; CVR_ERR_ARG for samples outside
+ * [0, CVR_VCT_MAX_SAMPLES], cone_step <= 0, an increase rate < 1 or an angle outside
+ * (0, 90). */
+cvr_status  cvr_render_vct(cvr_ctx* ctx, const cvr_frame* frame, const cvr_vct_params* params,
+                           const cvr_output* out);
 
 /* The reference renderers' default parameters for `variant`. */
 void        cvr_iso_params_default(int variant, cvr_iso_params* out);

@@ -367,6 +367,84 @@ cvr_status HipExtinctionBasedShading::RenderFrame (const cvr_output* out)
 }
 
 ////////////////////////////////////////////////////////////////////////////////
+// RC1PVoxelConeTracingSGPU (vctrenderer.cpp:27-250, preprocessingstages.cpp)
+////////////////////////////////////////////////////////////////////////////////
+HipVoxelConeTracingSGPU::HipVoxelConeTracingSGPU ()
+  : m_u_step_size(0.5f)
+  , m_apply_gradient_shading(false)
+  , apply_ambient_occlusion(true)              // vctrenderer.cpp:33-43
+  , apply_voxel_cone_tracing(true)
+  , cone_step_size(2.0f)
+  , cone_step_size_increase_rate(1.0f)
+  , cone_initial_step(2.0f)
+  , cone_apex_angle(2.0f)
+  , apply_correction_factor(true)
+  , opacity_correction_factor(2.0f)
+  , cone_number_of_samples(50)
+  , covered_distance(0.0f)
+  , m_params()
+{
+  cvr_vct_params_default(&m_params);
+}
+
+// The table integrates GetOpc(i, GetMaxDensity()) of the CPU transfer function
+// (preprocessingstages.cpp:153-173); the library builds the supervoxel pyramid on the
+// GPU and the table on the host (cvr_vct_precompute).
+bool HipVoxelConeTracingSGPU::UploadOpacities ()
+{
+  vis::TransferFunction* tf = m_ext_data_manager->GetCurrentTransferFunction();
+  std::vector<float> opc(CVR_VCT_TABLE_WIDTH);
+  for (size_t i = 0; i < opc.size(); i++) opc[i] = tf->GetOpc((double)i, 255.0);
+  if (cvr_vct_set_opacity(m_cvr, opc.data(), (int)opc.size()) != CVR_OK) return Fail("cvr_vct_set_opacity");
+  if (cvr_vct_precompute(m_cvr) != CVR_OK) return Fail("cvr_vct_precompute");
+  return true;
+}
+
+bool HipVoxelConeTracingSGPU::Init (int swidth, int sheight)
+{
+  if (IsBuilt()) Clean();
+  if (m_ext_data_manager->GetCurrentVolumeTexture() == nullptr) return false;
+  if (!UploadVolume() || !UploadTransferFunction() || !UploadGradient(m_apply_gradient_shading) ||
+      !UploadOpacities())
+    return false;
+  m_u_step_size = DefaultStep();                                               // :114-115
+  Reshape(swidth, sheight);
+  SetBuilt(true);
+  SetOutdated();
+  return true;
+}
+
+bool HipVoxelConeTracingSGPU::Update (vis::Camera* camera)
+{
+  vis::RenderingParameters* rp = m_ext_rendering_parameters;
+  FillFrame(camera);
+  m_params.step = m_u_step_size;
+  m_params.apply_gradient_shading =
+      (m_apply_gradient_shading && m_ext_data_manager->GetCurrentGradientTexture()) ? 1 : 0;
+  fill_phong(&m_params, rp);
+  copy3(m_params.light.position, rp->GetBlinnPhongLightingPosition());
+  copy3(m_params.light.forward, rp->GetBlinnPhongLightSourceCameraForward());
+  copy3(m_params.light.up, rp->GetBlinnPhongLightSourceCameraUp());
+  copy3(m_params.light.right, rp->GetBlinnPhongLightSourceCameraRight());
+  m_params.light.spot_angle_deg = rp->GetSpotLightMaxAngle();
+  m_params.apply_occlusion = apply_ambient_occlusion ? 1 : 0;
+  m_params.apply_shadow = apply_voxel_cone_tracing ? 1 : 0;
+  m_params.cone_step = cone_step_size;
+  m_params.cone_step_increase_rate = cone_step_size_increase_rate;
+  m_params.cone_initial_step = cone_initial_step;
+  m_params.cone_apex_angle_deg = cone_apex_angle;
+  m_params.apply_correction = apply_correction_factor ? 1 : 0;
+  m_params.correction_factor = opacity_correction_factor;
+  m_params.samples = cone_number_of_samples;
+  return true;
+}
+
+cvr_status HipVoxelConeTracingSGPU::RenderFrame (const cvr_output* out)
+{
+  return cvr_render_vct(m_cvr, &frame_, &m_params, out);
+}
+
+////////////////////////////////////////////////////////////////////////////////
 // The isosurface ray-casters (rc1pisoadapt, rc1pisocustom, rc1pisodfscustom)
 ////////////////////////////////////////////////////////////////////////////////
 HipIsoRayCasterBase::HipIsoRayCasterBase (int variant)

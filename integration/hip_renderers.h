@@ -8,6 +8,7 @@
  *   HipExtinctionBasedShading        <- RC1PExtinctionBasedShading
  *                                                              (rc1pextbsd/ebsrenderer.h:47-123)
  *   HipRC1PConeLightGroundTruthSteps <- RC1PConeLightGroundTruthSteps
+ *   HipVoxelConeTracingSGPU          <- RC1PVoxelConeTracingSGPU
  *                                                              (rc1pcrtgt/crtgtrenderer.h:50-118)
  *   HipRayCasting1PassIsoAdapt       <- RayCasting1PassIsoAdapt (rc1pisoadapt/rc1pisoadaptrenderer.h)
  *   HipCustomRayCasting1PassIsoAdapt <- CustomRayCasting1PassIsoAdapt (rc1pisocustom/...)
@@ -148,6 +149,39 @@ protected:
   cvr_status RenderFrame (const cvr_output* out) override;
   cvr_crtgt_params m_params;
   std::vector<float> m_occ_rays, m_sdw_rays;
+};
+
+// The third approximate shadow technique: one voxel cone toward the light per sample,
+// through a (mean, stddev) supervoxel pyramid and a pre-integration table (image-space
+// mode; the reference's light-cache mode of this renderer is not built).  1-byte
+// volumes only.
+class HipVoxelConeTracingSGPU : public HipRendererBase
+{
+public:
+  HipVoxelConeTracingSGPU ();
+  const char* GetName () override { return "1-Pass - Ray Casting - Voxel Cone Tracing (HIP, MI355X)"; }
+  const char* GetAbbreviationName () override { return "s_1rc_vct_hip"; }
+  bool Init (int shader_width, int shader_height) override;
+  bool Update (vis::Camera* camera) override;
+
+  // vctrenderer.cpp:27-43
+  float m_u_step_size;
+  bool m_apply_gradient_shading;
+  bool apply_ambient_occlusion;
+  bool apply_voxel_cone_tracing;
+  float cone_step_size;
+  float cone_step_size_increase_rate;
+  float cone_initial_step;
+  float cone_apex_angle;
+  bool apply_correction_factor;
+  float opacity_correction_factor;
+  int cone_number_of_samples;
+  float covered_distance;
+
+protected:
+  cvr_status RenderFrame (const cvr_output* out) override;
+  bool UploadOpacities ();             // GetOpc(i, 255) for the pre-integration table
+  cvr_vct_params m_params;
 };
 
 // The three single-pass isosurface ray-casters share one library entry point

@@ -19,6 +19,7 @@ void RegisterHipRenderers ()
   RenderingManager::Instance()->AddVolumeRenderer(new HipDirOcclusionShading());
   RenderingManager::Instance()->AddVolumeRenderer(new HipExtinctionBasedShading());
   RenderingManager::Instance()->AddVolumeRenderer(new HipRC1PConeLightGroundTruthSteps());
+  RenderingManager::Instance()->AddVolumeRenderer(new HipVoxelConeTracingSGPU());
   RenderingManager::Instance()->AddVolumeRenderer(new HipRayCasting1PassIsoAdapt());
   RenderingManager::Instance()->AddVolumeRenderer(new HipCustomRayCasting1PassIsoAdapt());
   RenderingManager::Instance()->AddVolumeRenderer(new HipCustomRayCasting1PassIsodfsAdapt());

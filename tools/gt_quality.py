@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""How far the approximate lighting paths are from the ground truth (DESIGN.md §5d′).
+"""How far the approximate lighting paths are from the ground truth (DESIGN.md §5d′, §5d″).
 
 On the bench scene at a reduced size (Marschner-Lobb --size^3 -> --res^2, the bonsai
-TF, the "Initial State" camera, light 0 of the reference's list) four frames are taken
+TF, the "Initial State" camera, light 0 of the reference's list) five frames are taken
 on one GPU:
 
   * the ground truth: cvr_render_crtgt with --rays secondary rays per term, the
@@ -11,7 +11,8 @@ on one GPU:
     shadow rays within its shadow cone's (0.5 deg), a point light;
   * cvr_render_dosct            (cone occlusion + point-light cone shadow, on the fly);
   * cvr_render_dosct_preillum   (the same through a 32^3 light cache);
-  * cvr_render_extbsd           (SAT occlusion + point-light SAT shadow).
+  * cvr_render_extbsd           (SAT occlusion + point-light SAT shadow);
+  * cvr_render_vct              (voxel cone tracing shadow, the reference's defaults).
 
 Prints the SSIM of each against the ground truth (cpp_volume_rendering_amd/ssim.py: the
 frames as screenshots over white) and the ground truth's time per frame, as a table and
@@ -32,8 +33,9 @@ from cpp_volume_rendering_amd import datasets as D  # noqa: E402
 from cpp_volume_rendering_amd.renderer import (Camera, DataManager,  # noqa: E402
                                                RC1PConeLightGroundTruthSteps,
                                                RC1PConeTracingDirOcclusionShading,
-                                               RC1PExtinctionBasedShading, RenderingParameters,
-                                               build_ext_lut, build_tf_rgbt)
+                                               RC1PExtinctionBasedShading, RC1PVoxelConeTracingSGPU,
+                                               RenderingParameters, build_ext_lut, build_opacity_lut,
+                                               build_tf_rgbt)
 from cpp_volume_rendering_amd.ssim import ssim_rgba  # noqa: E402
 
 
@@ -60,6 +62,7 @@ def main():
     dm.SetTransferFunction(build_tf_rgbt(D.BONSAI_TF_RGB, D.BONSAI_TF_ALPHA),
                            build_tf_rgbt(D.BONSAI_TF_RGB, D.BONSAI_TF_ALPHA, extinction_input=True))
     dm.SetExtinctionTable(build_ext_lut(D.BONSAI_TF_RGB, D.BONSAI_TF_ALPHA))
+    dm.SetOpacityTable(build_opacity_lut(D.BONSAI_TF_RGB, D.BONSAI_TF_ALPHA))
     rp = RenderingParameters(W, W, light_position=D.LIGHT_LIST0_POSITION)
     cam = Camera(**D.INITIAL_STATE_CAMERA)
 
@@ -87,7 +90,8 @@ def main():
         return r
 
     for name, r in (("cvr_render_dosct", dos(False)), ("cvr_render_dosct_preillum", dos(True)),
-                    ("cvr_render_extbsd", RC1PExtinctionBasedShading(0))):
+                    ("cvr_render_extbsd", RC1PExtinctionBasedShading(0)),
+                    ("cvr_render_vct", RC1PVoxelConeTracingSGPU(0))):
         r.SetExternalResources(dm, rp)
         assert r.Init(W, W)
         res["ssim"][name] = ssim_rgba(frame_of(r, cam), truth)
