@@ -34,6 +34,7 @@
 #include "cvr_device.h"
 #include "march_common.h"
 #include "shaded_march.h"
+#include "shade_common.h"
 
 namespace cvr {
 
@@ -217,33 +218,6 @@ __device__ float cone_rays(const CrtgtArgs& Q, const uint4* __restrict__ cells, 
   return sacc / swgt;
 }
 
-// ShadeSample (:254-302): the DOS renderer's combine (dos_cones.h) with vec3(1) for
-// the specular colour.  With both terms off 1 / (ka + kd) is inf and the colour NaN.
-__device__ __forceinline__ f3 gt_combine(const CrtgtArgs& Q, float iocc, float isdw, f3 wp, f3 rgb,
-                                         const f3* g) {
-  const Rc1passArgs& A = Q.a;
-  const float inv_k = 1.0f / (Q.ka + Q.kd);
-  if (g) {
-    if (g->x != 0.0f || g->y != 0.0f || g->z != 0.0f) {
-      const f3 eye{A.eye[0], A.eye[1], A.eye[2]};
-      const f3 light{A.light[0], A.light[1], A.light[2]};
-      const f3 nrm = normalize3(*g);
-      const f3 L = normalize3(f3{light.x - wp.x, light.y - wp.y, light.z - wp.z});
-      const f3 Ve = normalize3(f3{eye.x - wp.x, eye.y - wp.y, eye.z - wp.z});
-      const f3 Hv = normalize3(f3{Ve.x + L.x, Ve.y + L.y, Ve.z + L.z});
-      const float dd = fmaxf(0.0f, dot3(nrm, L));
-      const float ds = fmaxf(0.0f, dot3(Hv, nrm));
-      const float diff = inv_k * (iocc * Q.ka + (isdw * Q.kd) * dd);
-      const float spec = (isdw * Q.ks) * cvr_powf_nb(ds, A.shininess);
-      return f3{rgb.x * diff + spec, rgb.y * diff + spec, rgb.z * diff + spec};
-    }
-    return rgb;   // a zero gradient leaves the TF colour unshaded, as written
-  }
-  return f3{inv_k * ((rgb.x * iocc) * Q.ka + (rgb.x * isdw) * Q.kd),
-            inv_k * ((rgb.y * iocc) * Q.ka + (rgb.y * isdw) * Q.kd),
-            inv_k * ((rgb.z * iocc) * Q.ka + (rgb.z * isdw) * Q.kd)};
-}
-
 // Round step 2.  Persistent waves (4 per workgroup) stride over the round's list.
 template <int FB, bool PHONG>
 __global__ void __launch_bounds__(256)
@@ -277,6 +251,11 @@ crtgt_shade_kernel(CrtgtArgs Q, const uint4* __restrict__ cells, const float4* _
       iocc = cone_rays<FB>(Q, cells, tau, Q.occ_rays, Q.n_occ, Q.occ_distance, tx, v_right, v_up, v_dir, lane);
     }
     if (Q.apply_shadow) {
+      // Not shade_common.h's shadow_cone_frame, and not to be merged with it: this
+      // shader's (v_up, v_right) are not the DOS cone's (u, v) (DOS calls its cone
+      // with the two swapped), its axis is LightCamForward = -light.forward (lzaxs),
+      // and it tests the spot against the literal 30.0, not SpotLightMaxAngle: all
+      // as gt_ray_marching.comp (:171-252) is written.
       const f3 lz{Q.lzaxs[0], Q.lzaxs[1], Q.lzaxs[2]};
       f3 v_dir, v_up, v_right;
       bool on = true;
@@ -299,7 +278,9 @@ crtgt_shade_kernel(CrtgtArgs Q, const uint4* __restrict__ cells, const float4* _
       const float4 q2 = jp[2];
       g = f3{q2.x, q2.y, q2.z};
     }
-    const f3 c = gt_combine(Q, iocc, isdw, wp, f3{q1.x, q1.y, q1.z}, PHONG ? &g : nullptr);
+    // ShadeSample (:254-302): the DOS renderer's combine with vec3(1) for the specular
+    // colour (A.ispec, set by the host)
+    const f3 c = combine_cones(A, Q.ka, Q.kd, Q.ks, iocc, isdw, wp, f3{q1.x, q1.y, q1.z}, PHONG ? &g : nullptr);
     if (lane == 0) jp[1] = make_float4(c.x * q0.w, c.y * q0.w, c.z * q0.w, q1.w);
   }
 }

@@ -34,6 +34,18 @@ cvr_status fail(Ctx* c, cvr_status st, const char* fmt, ...) {
   return st;
 }
 
+void default_light(cvr_light* l) {
+  const float pos[3] = {-206.873f, -51.0699f, 557.011f}, fwd[3] = {-0.346883f, -0.0856335f, 0.933991f},
+              up[3] = {-0.0298143f, 0.996327f, 0.0802758f}, right[3] = {0.937434f, -0.0f, 0.348162f};
+  for (int i = 0; i < 3; i++) {
+    l->position[i] = pos[i];
+    l->forward[i] = fwd[i];
+    l->up[i] = up[i];
+    l->right[i] = right[i];
+  }
+  l->spot_angle_deg = 20.0f;
+}
+
 }  // namespace cvr
 
 // TransferFunction1D::BuildLinear + GenerateTexture_1D_RGBt

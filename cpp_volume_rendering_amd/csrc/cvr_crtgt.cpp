@@ -99,16 +99,14 @@ static cvr_status crtgt_begin(Ctx* c, const char* who, const cvr_frame* f, const
   Q.a.filter_bits = c->filter_bits;
   const float ispec[3] = {1.0f, 1.0f, 1.0f};   // `vec3(1) * (IShadow * ks * pow(...))`
   set_phong_constants(Q.a, p->ka, p->kd, p->ks, p->shininess, ispec, p->light.position);
-  for (int i = 0; i < 3; i++) Q.G[i] = (float)c->N[i] * c->scale[i];
+  grid_size(c, Q.G);
   Q.light_gap = p->light_gap;
   Q.light_step = p->light_step;
   Q.apply_occlusion = occ;
   Q.apply_shadow = sdw;
   Q.shadow_type = p->shadow_type;
   Q.phong = phong;
-  Q.ka = occ ? p->ka : 0.0f;
-  Q.kd = sdw ? p->kd : 0.0f;
-  Q.ks = sdw ? p->ks : 0.0f;
+  set_gated_weights(Q, occ, sdw, p->ka, p->kd, p->ks);
   // GetDiagonal() * 0.50f / 0.75f (crtgtrenderer.cpp:112-113), as the DOS cones' default
   const double vw = c->N[0] * (double)c->scale[0], vh = c->N[1] * (double)c->scale[1],
                vd = c->N[2] * (double)c->scale[2];
@@ -205,16 +203,7 @@ void cvr_crtgt_params_default(cvr_crtgt_params* p) {
   if (!p) return;
   *p = cvr_crtgt_params{};
   p->ka = 0.5f; p->kd = 0.5f; p->ks = 0.8f; p->shininess = 30.0f;   // renderingparameters.cpp:23-26
-  // light 0 of the reference's light list (the other renderers' default light)
-  const float pos[3] = {-206.873f, -51.0699f, 557.011f}, fwd[3] = {-0.346883f, -0.0856335f, 0.933991f},
-              up[3] = {-0.0298143f, 0.996327f, 0.0802758f}, right[3] = {0.937434f, -0.0f, 0.348162f};
-  for (int i = 0; i < 3; i++) {
-    p->light.position[i] = pos[i];
-    p->light.forward[i] = fwd[i];
-    p->light.up[i] = up[i];
-    p->light.right[i] = right[i];
-  }
-  p->light.spot_angle_deg = 20.0f;
+  default_light(&p->light);
   p->light_gap = 1.0f;    // m_u_light_ray_initial_step (:35)
   p->light_step = 0.5f;   // m_u_light_ray_step_size (:36)
 }

@@ -80,17 +80,14 @@ cvr_status dos_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_do
   Q.a.out_half = o && o->format == CVR_FORMAT_RGBA16F;
   // Phong ambient/diffuse/specular weights of the surface term
   set_phong_constants(Q.a, p->ka, p->kd, p->ks, p->shininess, p->ispecular, p->light.position);
-  for (int i = 0; i < 3; i++) Q.G[i] = (float)c->N[i] * c->scale[i];
+  grid_size(c, Q.G);
   Q.ext_levels = c->ext_levels;
   Q.levels = c->d_ext_levels;
   Q.apply_occlusion = p->apply_occlusion != 0;
   Q.apply_shadow = p->apply_shadow != 0;
   Q.shadow_type = p->shadow_type;
   Q.phong = phong;
-  // ShadeSample (:607-656): ka only with occlusion, kd/ks only with shadows
-  Q.ka = Q.apply_occlusion ? p->ka : 0.0f;
-  Q.kd = Q.apply_shadow ? p->kd : 0.0f;
-  Q.ks = Q.apply_shadow ? p->ks : 0.0f;
+  set_gated_weights(Q, Q.apply_occlusion != 0, Q.apply_shadow != 0, p->ka, p->kd, p->ks);   // ShadeSample (:607-656)
   for (int i = 0; i < 3; i++) {
     Q.lfwd[i] = p->light.forward[i];
     Q.lup[i] = p->light.up[i];
@@ -202,8 +199,8 @@ cvr_status cvr_set_extinction_volume(cvr_ctx* ctx, const float* tf_rgba, int n, 
       for (int i = 0; i < 3; i++) d[i] = std::max(1, res[i] >> L);
       lv[L].off = (int)off[L];
       lv[L].dx = d[0]; lv[L].dy = d[1]; lv[L].dz = d[2];
-      const float G[3] = {(float)c->N[0] * c->scale[0], (float)c->N[1] * c->scale[1],
-                          (float)c->N[2] * c->scale[2]};
+      float G[3];
+      grid_size(c, G);
       lv[L].sx = (float)d[0] / G[0];   // d / G, rounded once
       lv[L].sy = (float)d[1] / G[1];
       lv[L].sz = (float)d[2] / G[2];

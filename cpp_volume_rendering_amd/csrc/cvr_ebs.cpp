@@ -74,9 +74,9 @@ cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_eb
   }
   Q.a.out_half = o && o->format == CVR_FORMAT_RGBA16F;
   set_phong_constants(Q.a, p->ka, p->kd, p->ks, p->shininess, p->ispecular, p->light_pos);
+  grid_size(c, Q.G);
   for (int i = 0; i < 3; i++) {
     Q.S[i] = c->scale[i];
-    Q.G[i] = (float)c->N[i] * c->scale[i];
     Q.inv_vs[i] = 1.0f / (Q.G[i] + Q.S[i] * 2.0f);        // inv_vol_scaled (:75)
     Q.sat_dims[i] = c->sat_dims[i];
     Q.sat_pz = (uint32_t)c->sat_dims[0] * (uint32_t)c->sat_dims[1];
@@ -110,10 +110,7 @@ cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_eb
   Q.initial_step = p->shadow_initial_step;
   Q.ui_weight = p->shadow_ui_weight;
   Q.max_distance = ebs_max_distance(c, p);
-  // ShadeSample (:502-518): ka only with occlusion, kd/ks only with shadows
-  Q.ka = Q.apply_occlusion ? p->ka : 0.0f;
-  Q.kd = Q.apply_shadow ? p->kd : 0.0f;
-  Q.ks = Q.apply_shadow ? p->ks : 0.0f;
+  set_gated_weights(Q, Q.apply_occlusion != 0, Q.apply_shadow != 0, p->ka, p->kd, p->ks);   // ShadeSample (:502-518)
   return CVR_OK;
 }
 

@@ -1,7 +1,6 @@
 // cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
 // cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_crtgt.cpp,
-// cvr_iso.cpp)
-// share: error reporting, device-memory helpers, the half and vector helpers of
+// cvr_vct.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
 // the host arithmetic, and the frame set-up common to the renderers.  Host only:
 // never included by a .hip file or a kernel header.
 //
@@ -103,6 +102,24 @@ cvr_status check_frame_output(Ctx* c, const char* who, const cvr_frame* f, const
 // The Blinn-Phong constants of the surface term (ray_marching_1p.comp:48-81).
 void set_phong_constants(Rc1passArgs& A, float ka, float kd, float ks, float shininess,
                          const float ispec[3], const float light[3]);
+
+// VolumeGridSize (= VolumeScaledSizes) of the context's volume (rc1prenderer.cpp:241).
+inline void grid_size(const Ctx* c, float G[3]) {
+  for (int i = 0; i < 3; i++) G[i] = (float)c->N[i] * c->scale[i];
+}
+
+// ShadeSample's weights in a shaded renderer's kernel arguments: Kambient only with
+// occlusion, Kdiffuse / Kspecular only with shadows, else 0.
+template <class Args>
+void set_gated_weights(Args& Q, bool occlusion, bool shadow, float ka, float kd, float ks) {
+  Q.ka = occlusion ? ka : 0.0f;
+  Q.kd = shadow ? kd : 0.0f;
+  Q.ks = shadow ? ks : 0.0f;
+}
+
+// cvr_api.cpp: light 0 of the reference's light list, the default light of the
+// renderers that take a cvr_light
+void default_light(cvr_light* l);
 
 // With option "cell_skip" on: the march uses the cells' skip flags at `level`
 // (built here when stale).  Without memory for the build the frame renders

@@ -124,8 +124,8 @@ cvr_status cvr_render_iso(cvr_ctx* ctx, const cvr_frame* f, const cvr_iso_params
   fill_frame_args(c, f, 1.0f, Q.a, ntiles, npix);
   Q.a.out_half = o->format == CVR_FORMAT_RGBA16F;
   set_phong_constants(Q.a, p->ka, p->kd, p->ks, p->shininess, p->ispecular, p->light_pos);
+  grid_size(c, Q.G);
   for (int i = 0; i < 3; i++) {
-    Q.G[i] = (float)c->N[i] * c->scale[i];
     Q.nb[i] = (float)nb[i];
     Q.nbi[i] = nb[i];
   }

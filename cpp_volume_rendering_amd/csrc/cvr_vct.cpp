@@ -158,17 +158,8 @@ void cvr_vct_params_default(cvr_vct_params* p) {
   if (!p) return;
   *p = cvr_vct_params{};
   p->ka = 0.5f; p->kd = 0.5f; p->ks = 0.8f; p->shininess = 30.0f;   // renderingparameters.cpp:23-26
-  // light 0 of the reference's light list (the other renderers' default light)
-  const float pos[3] = {-206.873f, -51.0699f, 557.011f}, fwd[3] = {-0.346883f, -0.0856335f, 0.933991f},
-              up[3] = {-0.0298143f, 0.996327f, 0.0802758f}, right[3] = {0.937434f, -0.0f, 0.348162f};
-  for (int i = 0; i < 3; i++) {
-    p->ispecular[i] = 1.0f;
-    p->light.position[i] = pos[i];
-    p->light.forward[i] = fwd[i];
-    p->light.up[i] = up[i];
-    p->light.right[i] = right[i];
-  }
-  p->light.spot_angle_deg = 20.0f;
+  for (int i = 0; i < 3; i++) p->ispecular[i] = 1.0f;
+  default_light(&p->light);
   // vctrenderer.cpp:33-43
   p->apply_occlusion = 1;
   p->apply_shadow = 1;
@@ -315,13 +306,10 @@ cvr_status cvr_render_vct(cvr_ctx* ctx, const cvr_frame* f, const cvr_vct_params
   if ((st = enable_cell_skip(c, Q.a, 1)) != CVR_OK) return st;   // the per-cell skip flags in the count / emit march
   Q.a.out_half = o->format == CVR_FORMAT_RGBA16F;
   set_phong_constants(Q.a, p->ka, p->kd, p->ks, p->shininess, p->ispecular, p->light.position);
-  for (int i = 0; i < 3; i++) Q.G[i] = (float)c->N[i] * c->scale[i];
+  grid_size(c, Q.G);
   Q.apply_shadow = p->apply_shadow != 0;
   Q.phong = phong;
-  // ShadeSample (:150-161): ka only with occlusion, kd / ks only with the shadow
-  Q.ka = p->apply_occlusion ? p->ka : 0.0f;
-  Q.kd = Q.apply_shadow ? p->kd : 0.0f;
-  Q.ks = Q.apply_shadow ? p->ks : 0.0f;
+  set_gated_weights(Q, p->apply_occlusion != 0, Q.apply_shadow != 0, p->ka, p->kd, p->ks);   // ShadeSample (:150-161)
   Q.samples = p->samples;
   Q.tab_wi = CVR_VCT_TABLE_WIDTH;
   Q.tab_hi = v.tab_h;

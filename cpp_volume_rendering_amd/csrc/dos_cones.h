@@ -15,6 +15,7 @@
 #include "cvr_device.h"
 #include "march_common.h"
 #include "shaded_march.h"
+#include "shade_common.h"
 
 namespace cvr {
 
@@ -385,22 +386,9 @@ struct DosShaderT {
       wp = world_pos(Q, tx);
     }
     if (Q.apply_shadow) {
-      const f3 light{A.light[0], A.light[1], A.light[2]};
       f3 k, u, v;
-      bool on = true;
-      const f3 lf{Q.lfwd[0], Q.lfwd[1], Q.lfwd[2]};
-      if (Q.shadow_type == 2) {
-        k = lf;
-        v = f3{Q.lup[0], Q.lup[1], Q.lup[2]};
-        u = f3{Q.lright[0], Q.lright[1], Q.lright[2]};
-      } else {
-        k = normalize3(f3{light.x - wp.x, light.y - wp.y, light.z - wp.z});
-        u = normalize3(cross3(k, f3{Q.lright[0], Q.lright[1], Q.lright[2]}));
-        v = normalize3(cross3(k, u));
-        if (Q.shadow_type == 1 && dot3(k, lf) < Q.spot_cos) on = false;
-      }
       // Cone1RayShadow(pos, k, v, u) is called as (pos, k, u, v): swapped (:559-561)
-      if (on) {
+      if (shadow_cone_frame(Q, wp, k, u, v)) {
         r.isdw = cone_trace<FB>(Q, Q.sdw, ext, tx, k, v, u, fetches);
         lit++;
       }
@@ -408,28 +396,7 @@ struct DosShaderT {
     return r;
   }
   __device__ static __forceinline__ f3 combine(const DosArgs& Q, Vis r, f3 wp, f3 rgb, const f3* g) {
-    const Rc1passArgs& A = Q.a;
-    const float inv_k = 1.0f / (Q.ka + Q.kd);
-    if (g) {   // ApplyPhongShading
-      if (g->x != 0.0f || g->y != 0.0f || g->z != 0.0f) {
-        const f3 eye{A.eye[0], A.eye[1], A.eye[2]};
-        const f3 light{A.light[0], A.light[1], A.light[2]};
-        const f3 nrm = normalize3(*g);
-        const f3 L = normalize3(f3{light.x - wp.x, light.y - wp.y, light.z - wp.z});
-        const f3 Ve = normalize3(f3{eye.x - wp.x, eye.y - wp.y, eye.z - wp.z});
-        const f3 Hv = normalize3(f3{Ve.x + L.x, Ve.y + L.y, Ve.z + L.z});
-        const float dd = fmaxf(0.0f, dot3(nrm, L));
-        const float ds = fmaxf(0.0f, dot3(Hv, nrm));
-        const float diff = inv_k * (r.iocc * Q.ka + (r.isdw * Q.kd) * dd);
-        const float spec = (r.isdw * Q.ks) * cvr_powf_nb(ds, A.shininess);
-        return f3{fmaf(A.ispec[0], spec, rgb.x * diff), fmaf(A.ispec[1], spec, rgb.y * diff),
-                  fmaf(A.ispec[2], spec, rgb.z * diff)};
-      }
-      return rgb;
-    }
-    return f3{inv_k * ((rgb.x * r.iocc) * Q.ka + (rgb.x * r.isdw) * Q.kd),
-              inv_k * ((rgb.y * r.iocc) * Q.ka + (rgb.y * r.isdw) * Q.kd),
-              inv_k * ((rgb.z * r.iocc) * Q.ka + (rgb.z * r.isdw) * Q.kd)};
+    return combine_cones(Q.a, Q.ka, Q.kd, Q.ks, r.iocc, r.isdw, wp, rgb, g);
   }
   // Forced inline: as a call (the inliner's choice for filter_bits 8, or after small
   // changes to the taps) the kernel-argument block Q is copied to scratch, ~1.9 KB

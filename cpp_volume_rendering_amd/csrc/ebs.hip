@@ -17,6 +17,7 @@
 #include "cvr_device.h"
 #include "march_common.h"
 #include "shaded_march.h"
+#include "shade_common.h"
 #include "ebs_sat.h"
 
 namespace cvr {
@@ -40,7 +41,6 @@ struct EbsShaderT {
   __device__ static f3 shade(const EbsArgs& Q, typename LY::Ptr __restrict__ sat, f3 tx, f3 wp, f3,
                              f3 rgb, const f3* g, uint32_t& lit, uint32_t& fetches) {
     const Rc1passArgs& A = Q.a;
-    const f3 eye{A.eye[0], A.eye[1], A.eye[2]};
     const f3 light{A.light[0], A.light[1], A.light[2]};
     float iocc = 0.0f, isdw = 0.0f;
     if (Q.apply_occlusion) {
@@ -56,26 +56,7 @@ struct EbsShaderT {
       isdw = cvr_expf(-Stau);
       lit++;
     }
-    const float inv_k = 1.0f / (Q.ka + Q.kd);
-    if (g) {   // ApplyPhongShading
-      if (g->x != 0.0f || g->y != 0.0f || g->z != 0.0f) {
-        const f3 nrm = normalize3(*g);
-        const f3 L = normalize3(f3{light.x - wp.x, light.y - wp.y, light.z - wp.z});
-        const f3 Ve = normalize3(f3{eye.x - wp.x, eye.y - wp.y, eye.z - wp.z});
-        const f3 Hv = normalize3(f3{Ve.x + L.x, Ve.y + L.y, Ve.z + L.z});
-        const float dd = fmaxf(0.0f, dot3(nrm, L));
-        const float ds = fmaxf(0.0f, dot3(Hv, nrm));
-        const float pw = cvr_powf_nb(ds, A.shininess);
-        // (1/(ka+kd)) * (L*IOcc*ka + IShadow*(L*kd*dot_diff)) + IShadow*(ks*Ispecular*pow) (:528-530)
-        return f3{inv_k * ((rgb.x * iocc) * Q.ka + isdw * ((rgb.x * Q.kd) * dd)) + isdw * ((Q.ks * A.ispec[0]) * pw),
-                  inv_k * ((rgb.y * iocc) * Q.ka + isdw * ((rgb.y * Q.kd) * dd)) + isdw * ((Q.ks * A.ispec[1]) * pw),
-                  inv_k * ((rgb.z * iocc) * Q.ka + isdw * ((rgb.z * Q.kd) * dd)) + isdw * ((Q.ks * A.ispec[2]) * pw)};
-      }
-      return rgb;
-    }
-    return f3{inv_k * ((rgb.x * iocc) * Q.ka + (rgb.x * isdw) * Q.kd),
-              inv_k * ((rgb.y * iocc) * Q.ka + (rgb.y * isdw) * Q.kd),
-              inv_k * ((rgb.z * iocc) * Q.ka + (rgb.z * isdw) * Q.kd)};
+    return combine_sat(A, Q.ka, Q.kd, Q.ks, iocc, isdw, wp, rgb, g);
   }
 };
 

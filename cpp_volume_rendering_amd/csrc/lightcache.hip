@@ -64,18 +64,7 @@ light_cache_kernel(DosArgs Q, LightCacheArgs P, const uint4* __restrict__ ext,
   if (Q.apply_shadow) {
     // ShadowEvaluationKernel (:492-521)
     f3 k, u, v;
-    bool on = true;
-    const f3 lf{Q.lfwd[0], Q.lfwd[1], Q.lfwd[2]};
-    if (Q.shadow_type == 2) {
-      k = lf;
-      v = f3{Q.lup[0], Q.lup[1], Q.lup[2]};
-      u = f3{Q.lright[0], Q.lright[1], Q.lright[2]};
-    } else {
-      k = normalize3(f3{A.light[0] - wp.x, A.light[1] - wp.y, A.light[2] - wp.z});
-      u = normalize3(cross3(k, f3{Q.lright[0], Q.lright[1], Q.lright[2]}));
-      v = normalize3(cross3(k, u));
-      if (Q.shadow_type == 1 && dot3(k, lf) < Q.spot_cos) on = false;
-    }
+    const bool on = shadow_cone_frame(Q, wp, k, u, v);
     // Cone1RayShadow(pos, k, v, u) is called as (pos, k, u, v): swapped, as on the fly
     idcs = on ? cone_trace<M>(Q, Q.sdw, ext, tx, k, v, u, nf) : 0.0f;
   }
@@ -114,32 +103,10 @@ struct PreillumShaderT {
     return Q.apply_occlusion != 0 || Q.apply_shadow != 0;
   }
 
-  // texture(TexVolumeLightCache, tx_pos / VolumeScaledSizes).rg: GL_LINEAR,
-  // clamp-to-edge, texel coordinate fma(p, L / G, -0.5) (the convention of every
-  // other fetch here; clamping to [0, L - 1] gives GL's values, see sample_pos)
+  // texture(TexVolumeLightCache, tx_pos / VolumeScaledSizes).rg (dims <= 512 per
+  // axis, checked on the host)
   __device__ static __forceinline__ void fetch(const LightCacheView& C, f3 p, float& r, float& g) {
-    const float x = __builtin_amdgcn_fmed3f(fmaf(p.x, C.s[0], -0.5f), 0.0f, C.m[0]);
-    const float y = __builtin_amdgcn_fmed3f(fmaf(p.y, C.s[1], -0.5f), 0.0f, C.m[1]);
-    const float z = __builtin_amdgcn_fmed3f(fmaf(p.z, C.s[2], -0.5f), 0.0f, C.m[2]);
-    const int ix = (int)x, iy = (int)y, iz = (int)z;
-    const float ax = filter_weight<kFB>(__builtin_amdgcn_fractf(x));
-    const float ay = filter_weight<kFB>(__builtin_amdgcn_fractf(y));
-    const float az = filter_weight<kFB>(__builtin_amdgcn_fractf(z));
-    const int x1 = min(ix + 1, C.d[0] - 1), y1 = min(iy + 1, C.d[1] - 1), z1 = min(iz + 1, C.d[2] - 1);
-    // dims <= 512 per axis (checked on the host): 32-bit indices
-    const int sy = C.d[0], sz = C.d[0] * C.d[1];
-    const int r00 = iz * sz + iy * sy, r10 = iz * sz + y1 * sy;
-    const int r01 = z1 * sz + iy * sy, r11 = z1 * sz + y1 * sy;
-    const uint32_t t000 = C.rg[r00 + ix], t100 = C.rg[r00 + x1], t010 = C.rg[r10 + ix],
-                   t110 = C.rg[r10 + x1], t001 = C.rg[r01 + ix], t101 = C.rg[r01 + x1],
-                   t011 = C.rg[r11 + ix], t111 = C.rg[r11 + x1];
-    float a[8], c[8];
-    h2f2(t000, a[0], c[0]); h2f2(t100, a[1], c[1]); h2f2(t010, a[2], c[2]); h2f2(t110, a[3], c[3]);
-    h2f2(t001, a[4], c[4]); h2f2(t101, a[5], c[5]); h2f2(t011, a[6], c[6]); h2f2(t111, a[7], c[7]);
-    r = lerpf(lerpf(lerpf(a[0], a[1], ax), lerpf(a[2], a[3], ax), ay),
-              lerpf(lerpf(a[4], a[5], ax), lerpf(a[6], a[7], ax), ay), az);
-    g = lerpf(lerpf(lerpf(c[0], c[1], ax), lerpf(c[2], c[3], ax), ay),
-              lerpf(lerpf(c[4], c[5], ax), lerpf(c[6], c[7], ax), ay), az);
+    fetch_rg16<kFB>(C.rg, C.d, C.s, C.m, p, r, g);
   }
 
   __device__ static __forceinline__ f3 shade(const DosArgs& Q, const LightCacheView& C, f3 tx, f3 wp, f3 cam,

@@ -29,6 +29,7 @@
 #include "cvr_device.h"
 #include "march_common.h"
 #include "shaded_march.h"
+#include "shade_common.h"
 
 namespace cvr {
 
@@ -76,33 +77,11 @@ struct VctShaderT {
   static constexpr bool kSplit = false;       // flat_shade_kernel calls shade() whole
   static constexpr int kFB = FB;              // GL_LINEAR weights of every fetch (filter_bits)
 
-  // texture(level, p / G).rg: GL_LINEAR, clamp-to-edge, texel coordinate
-  // fma(p, d / G, -0.5); clamping to [0, d - 1] gives Tex::sample's values (a
-  // coordinate in [-1, 0) reads texel 0 with any weight; the texels are finite)
+  // texture(level, p / G).rg = (mean, standard deviation); the pyramid holds < 2^31
+  // texels (checked on the host) and they are finite
   __device__ static __forceinline__ void fetch_level(const uint32_t* __restrict__ pyr, const VctLevel& L,
                                                      f3 p, float& mean, float& sd) {
-    const float x = __builtin_amdgcn_fmed3f(fmaf(p.x, L.s[0], -0.5f), 0.0f, L.m[0]);
-    const float y = __builtin_amdgcn_fmed3f(fmaf(p.y, L.s[1], -0.5f), 0.0f, L.m[1]);
-    const float z = __builtin_amdgcn_fmed3f(fmaf(p.z, L.s[2], -0.5f), 0.0f, L.m[2]);
-    const int ix = (int)x, iy = (int)y, iz = (int)z;
-    const float ax = filter_weight<FB>(__builtin_amdgcn_fractf(x));
-    const float ay = filter_weight<FB>(__builtin_amdgcn_fractf(y));
-    const float az = filter_weight<FB>(__builtin_amdgcn_fractf(z));
-    const int x1 = min(ix + 1, L.d[0] - 1), y1 = min(iy + 1, L.d[1] - 1), z1 = min(iz + 1, L.d[2] - 1);
-    // the pyramid holds < 2^31 texels (checked on the host): 32-bit indices
-    const int sy = L.d[0], sz = L.d[0] * L.d[1];
-    const uint32_t* t = pyr + L.off;
-    const int r00 = iz * sz + iy * sy, r10 = iz * sz + y1 * sy;
-    const int r01 = z1 * sz + iy * sy, r11 = z1 * sz + y1 * sy;
-    const uint32_t t000 = t[r00 + ix], t100 = t[r00 + x1], t010 = t[r10 + ix], t110 = t[r10 + x1],
-                   t001 = t[r01 + ix], t101 = t[r01 + x1], t011 = t[r11 + ix], t111 = t[r11 + x1];
-    float a[8], c[8];
-    h2f2(t000, a[0], c[0]); h2f2(t100, a[1], c[1]); h2f2(t010, a[2], c[2]); h2f2(t110, a[3], c[3]);
-    h2f2(t001, a[4], c[4]); h2f2(t101, a[5], c[5]); h2f2(t011, a[6], c[6]); h2f2(t111, a[7], c[7]);
-    mean = lerpf(lerpf(lerpf(a[0], a[1], ax), lerpf(a[2], a[3], ax), ay),
-                 lerpf(lerpf(a[4], a[5], ax), lerpf(a[6], a[7], ax), ay), az);
-    sd = lerpf(lerpf(lerpf(c[0], c[1], ax), lerpf(c[2], c[3], ax), ay),
-               lerpf(lerpf(c[4], c[5], ax), lerpf(c[6], c[7], ax), ay), az);
+    fetch_rg16<FB>(pyr + L.off, L.d, L.s, L.m, p, mean, sd);
   }
 
   // texture(TexPreIntegrationLookup, uv).r: GL_LINEAR, clamp-to-edge, texel
@@ -152,34 +131,13 @@ struct VctShaderT {
   // ShadeSample (:146-189); `lit` counts the cones traced.
   __device__ static __forceinline__ f3 shade(const VctArgs& Q, VctData D, f3 tx, f3 wp, f3, f3 rgb,
                                              const f3* g, uint32_t& lit, uint32_t& fetches) {
-    const Rc1passArgs& A = Q.a;
     float ivd = 0.0f;
     if (Q.apply_shadow) {
       ivd = cone(Q, D, tx, wp, fetches);
       lit++;
     }
-    const float inv_k = 1.0f / (Q.ka + Q.kd);
-    if (g) {   // ApplyPhongShading
-      if (g->x != 0.0f || g->y != 0.0f || g->z != 0.0f) {
-        const f3 eye{A.eye[0], A.eye[1], A.eye[2]};
-        const f3 light{A.light[0], A.light[1], A.light[2]};
-        const f3 nrm = normalize3(*g);
-        const f3 L = normalize3(f3{light.x - wp.x, light.y - wp.y, light.z - wp.z});
-        const f3 Ve = normalize3(f3{eye.x - wp.x, eye.y - wp.y, eye.z - wp.z});
-        const f3 Hv = normalize3(f3{Ve.x + L.x, Ve.y + L.y, Ve.z + L.z});
-        const float dd = fmaxf(0.0f, dot3(nrm, L));
-        const float ds = fmaxf(0.0f, dot3(Hv, nrm));
-        const float pw = cvr_powf_nb(ds, A.shininess);
-        // (1/(ka+kd)) * (L*ka + Ivd*(L*kd*dot_diff)) + Ivd*(ks*Ispecular*pow) (:179-180)
-        return f3{inv_k * (rgb.x * Q.ka + ivd * ((rgb.x * Q.kd) * dd)) + ivd * ((Q.ks * A.ispec[0]) * pw),
-                  inv_k * (rgb.y * Q.ka + ivd * ((rgb.y * Q.kd) * dd)) + ivd * ((Q.ks * A.ispec[1]) * pw),
-                  inv_k * (rgb.z * Q.ka + ivd * ((rgb.z * Q.kd) * dd)) + ivd * ((Q.ks * A.ispec[2]) * pw)};
-      }
-      return rgb;
-    }
-    // (1/(ka+kd)) * (L*ka + L*Ivd*kd) (:185)
-    return f3{inv_k * (rgb.x * Q.ka + (rgb.x * ivd) * Q.kd), inv_k * (rgb.y * Q.ka + (rgb.y * ivd) * Q.kd),
-              inv_k * (rgb.z * Q.ka + (rgb.z * ivd) * Q.kd)};
+    // (:179-180, :185) the EBS tail without an occlusion term: L*ka is (L*1)*ka exactly
+    return combine_sat(Q.a, Q.ka, Q.kd, Q.ks, 1.0f, ivd, wp, rgb, g);
   }
 };
 

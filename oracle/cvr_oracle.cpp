@@ -748,6 +748,86 @@ float cone_trace(const ExtVol& E, const OracleDosCone& C, v3 pos, v3 k, v3 u, v3
 
 namespace {
 
+// ---------------------------------------------------------------------------
+// The tail of ShadeSample, shared by the shaded renderers and by the CPU
+// references under tests/support/ that include this translation unit.  ka, kd, ks
+// are gated (ka only with occlusion, kd / ks only with shadows); with both off
+// 1 / (ka + kd) is inf and the colour NaN, as in the reference.  g: the gradient
+// sample with Phong shading on, else null; a zero gradient leaves src unshaded.
+// ---------------------------------------------------------------------------
+
+// The gradient sample of ApplyPhongShading at texel (x, y, z) into g, or null without it.
+inline const float* shading_gradient(const OracleRc1pass& P, float x, float y, float z, float g[3]) {
+  if (!(P.phong && P.grad)) return nullptr;
+  Tex{P.grad, {P.N[0], P.N[1], P.N[2]}, 3, P.filter_bits}.sample(x, y, z, g);
+  return g;
+}
+
+struct PhongTerms { float dd, pw; };   // max(0, N.L), pow(max(0, H.N), shininess)
+inline PhongTerms phong_terms(const OracleRc1pass& P, v3 wp, const float* g) {
+  const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
+  const v3 light = mk(P.light[0], P.light[1], P.light[2]);
+  const v3 n = normalize3(mk(g[0], g[1], g[2]));
+  const v3 L = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
+  const v3 Ve = normalize3(mk(eye.x - wp.x, eye.y - wp.y, eye.z - wp.z));
+  const v3 Hv = normalize3(mk(Ve.x + L.x, Ve.y + L.y, Ve.z + L.z));
+  const float dd = std::fmax(0.0f, dot3(n, L));
+  const float ds = std::fmax(0.0f, dot3(Hv, n));
+  return PhongTerms{dd, cvr_powf(ds, P.shininess)};
+}
+
+inline bool nonzero3(const float* g) { return g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f; }
+
+// (1/(ka+kd)) * (L*IOcc*ka + L*IShadow*kd): every shader's colour without Phong shading
+inline void combine_unshaded(float inv_k, float ka, float kd, float iocc, float isdw, float* src) {
+  for (int q = 0; q < 3; q++) src[q] = inv_k * ((src[q] * iocc) * ka + (src[q] * isdw) * kd);
+}
+
+// The cone form (rc1pdosct :607-656 and its cached march, rc1pcrtgt with Ispecular = vec3(1)):
+//   L * ((1/(ka+kd)) * (IOcc*ka + IShadow*kd*dot_diff)) + Ispecular * (IShadow*ks*pow)
+inline void combine_cones(const OracleRc1pass& P, float ka, float kd, float ks, float iocc, float isdw,
+                          v3 wp, float* src, const float* g) {
+  const float inv_k = 1.0f / (ka + kd);
+  if (!g) return combine_unshaded(inv_k, ka, kd, iocc, isdw, src);
+  if (!nonzero3(g)) return;
+  const PhongTerms t = phong_terms(P, wp, g);
+  const float diff = inv_k * (iocc * ka + (isdw * kd) * t.dd);
+  const float spec = (isdw * ks) * t.pw;
+  for (int q = 0; q < 3; q++) src[q] = std::fmaf(P.ispec[q], spec, src[q] * diff);
+}
+
+// The SAT form (rc1pextbsd :528-530, rc1pvctsg :179-180 with IOcc = 1):
+//   (1/(ka+kd)) * (L*IOcc*ka + IShadow*(L*kd*dot_diff)) + IShadow*(ks*Ispecular*pow)
+inline void combine_sat(const OracleRc1pass& P, float ka, float kd, float ks, float iocc, float isdw,
+                        v3 wp, float* src, const float* g) {
+  const float inv_k = 1.0f / (ka + kd);
+  if (!g) return combine_unshaded(inv_k, ka, kd, iocc, isdw, src);
+  if (!nonzero3(g)) return;
+  const PhongTerms t = phong_terms(P, wp, g);
+  for (int q = 0; q < 3; q++)
+    src[q] = inv_k * ((src[q] * iocc) * ka + isdw * ((src[q] * kd) * t.dd)) + isdw * ((ks * P.ispec[q]) * t.pw);
+}
+
+// The frame (k, u, v) of the DOS shadow cone at wp (ShadowEvaluationKernel,
+// ray_bbox_marching.comp:533-562, lightcachecomputation.comp:492-521): the light
+// camera's vectors for a directional light (shadow_type 2), else the axis toward
+// the light and two crosses.  False where a spot light (type 1) does not reach wp.
+// SpotLightMaxAngle uniform: glm::cos(glm::pi<float>() * angle / 180.f) (dosrcrenderer.cpp:158)
+inline float dos_spot_cos(const OracleDos* Q) { return std::cos(3.14159265358979323846f * Q->spot_angle_deg / 180.0f); }
+inline bool shadow_cone_frame(const OracleDos* Q, float spot_cos, v3 wp, v3& k, v3& u, v3& v) {
+  const float* l = Q->base.light;
+  const v3 lfwd = mk(Q->light_forward[0], Q->light_forward[1], Q->light_forward[2]);
+  const v3 lright = mk(Q->light_right[0], Q->light_right[1], Q->light_right[2]);
+  if (Q->shadow_type == 2) {
+    k = lfwd; v = mk(Q->light_up[0], Q->light_up[1], Q->light_up[2]); u = lright;
+    return true;
+  }
+  k = normalize3(mk(l[0] - wp.x, l[1] - wp.y, l[2] - wp.z));
+  u = normalize3(cross3(k, lright));
+  v = normalize3(cross3(k, u));
+  return !(Q->shadow_type == 1 && dot3(k, lfwd) < spot_cos);
+}
+
 // The single-pass march shared by the shaded renderers (ray_bbox_marching.comp
 // :658-734, ebs_ray_bbox_marching.comp:552-625): rows [y0, y1) of the frame.
 // For every sample with alpha > 0, shade(src, tx, wp, cam_dir, x, y, z) turns
@@ -842,11 +922,7 @@ ORACLE_API uint64_t oracle_render_dos_rows(const OracleDos* Q, int y0, int y1, f
   const OracleRc1pass& P = Q->base;
   const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
   const v3 G = mk((float)P.N[0] * P.scale[0], (float)P.N[1] * P.scale[1], (float)P.N[2] * P.scale[2]);
-  const v3 light = mk(P.light[0], P.light[1], P.light[2]);
-  const v3 lfwd = mk(Q->light_forward[0], Q->light_forward[1], Q->light_forward[2]);
-  const v3 lup = mk(Q->light_up[0], Q->light_up[1], Q->light_up[2]);
-  const v3 lright = mk(Q->light_right[0], Q->light_right[1], Q->light_right[2]);
-  Tex grd{P.grad, {P.N[0], P.N[1], P.N[2]}, 3, P.filter_bits};
+  const float spot_cos = dos_spot_cos(Q);
   ExtVol E{Q->ext, {Q->ext_res[0], Q->ext_res[1], Q->ext_res[2]}, Q->ext_levels, G, {}, P.filter_bits};
   E.off.assign(E.nl + 1, 0);
   for (int L = 0; L < E.nl; L++) {
@@ -854,8 +930,6 @@ ORACLE_API uint64_t oracle_render_dos_rows(const OracleDos* Q, int y0, int y1, f
     ext_level_dims(E.res, L, d);
     E.off[L + 1] = E.off[L] + (int64_t)d[0] * d[1] * d[2];
   }
-  // SpotLightMaxAngle uniform: glm::cos(glm::pi<float>() * angle / 180.f) (dosrcrenderer.cpp:158)
-  const float spot_cos = std::cos(3.14159265358979323846f * Q->spot_angle_deg / 180.0f);
   const float ka = Q->apply_occlusion ? P.ka : 0.0f;
   const float kd = Q->apply_shadow ? P.kd : 0.0f;
   const float ks = Q->apply_shadow ? P.ks : 0.0f;
@@ -870,36 +944,12 @@ ORACLE_API uint64_t oracle_render_dos_rows(const OracleDos* Q, int y0, int y1, f
     }
     if (Q->apply_shadow) {
       v3 k, u, v;
-      bool lit = true;
-      if (Q->shadow_type == 2) {
-        k = lfwd; v = lup; u = lright;
-      } else {
-        k = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-        u = normalize3(cross3(k, lright));
-        v = normalize3(cross3(k, u));
-        if (Q->shadow_type == 1 && dot3(k, lfwd) < spot_cos) lit = false;
-      }
+      const bool lit = shadow_cone_frame(Q, spot_cos, wp, k, u, v);
       // Cone1RayShadow(pos, k, v, u) is called as (pos, k, u, v): swapped (:559-561)
       isdw = lit ? cone_trace(E, Q->sdw, tx, k, v, u) : 0.0f;
     }
-    const float inv_k = 1.0f / (ka + kd);
-    if (P.phong && P.grad) {
-      float g[3];
-      grd.sample(x, y, z, g);
-      if (g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f) {
-        const v3 n = normalize3(mk(g[0], g[1], g[2]));
-        const v3 L = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-        const v3 Ve = normalize3(mk(eye.x - wp.x, eye.y - wp.y, eye.z - wp.z));
-        const v3 Hv = normalize3(mk(Ve.x + L.x, Ve.y + L.y, Ve.z + L.z));
-        const float dd = std::fmax(0.0f, dot3(n, L));
-        const float ds = std::fmax(0.0f, dot3(Hv, n));
-        const float diff = inv_k * (iocc * ka + (isdw * kd) * dd);
-        const float spec = (isdw * ks) * cvr_powf(ds, P.shininess);
-        for (int q = 0; q < 3; q++) src[q] = std::fmaf(P.ispec[q], spec, src[q] * diff);
-      }
-    } else {
-      for (int q = 0; q < 3; q++) src[q] = inv_k * ((src[q] * iocc) * ka + (src[q] * isdw) * kd);
-    }
+    float g[3];
+    combine_cones(P, ka, kd, ks, iocc, isdw, wp, src, shading_gradient(P, x, y, z, g));
   };
   return shaded_march_rows(P, y0, y1, out_rgba, out_counts, nthreads, shade);
 }
@@ -1203,7 +1253,6 @@ float cone_x(const Sat& T, const OracleEbs& Q, const ConeCS& c, v3 pos, v3 cv) {
 ORACLE_API uint64_t oracle_render_ebs_rows(const OracleEbs* Q, int y0, int y1, float* out_rgba,
                                            uint32_t* out_counts, int nthreads) {
   const OracleRc1pass& P = Q->base;
-  const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
   const v3 light = mk(P.light[0], P.light[1], P.light[2]);
   Sat T;
   T.t = Tex{Q->sat, {Q->sat_dims[0], Q->sat_dims[1], Q->sat_dims[2]}, 1, P.filter_bits};
@@ -1217,7 +1266,6 @@ ORACLE_API uint64_t oracle_render_ebs_rows(const OracleEbs* Q, int y0, int y1, f
   ConeCS cs{std::cos(Q->cone_angle), std::sin(Q->cone_angle), std::cos(-Q->cone_angle),
             std::sin(-Q->cone_angle)};
   const v3 lfwd = mk(Q->light_forward[0], Q->light_forward[1], Q->light_forward[2]);
-  Tex grd{P.grad, {P.N[0], P.N[1], P.N[2]}, 3, P.filter_bits};
   const float ka = Q->apply_occlusion ? P.ka : 0.0f;
   const float kd = Q->apply_shadow ? P.kd : 0.0f;
   const float ks = Q->apply_shadow ? P.ks : 0.0f;
@@ -1235,26 +1283,8 @@ ORACLE_API uint64_t oracle_render_ebs_rows(const OracleEbs* Q, int y0, int y1, f
       else Stau = cone_x(T, *Q, cs, tx, cv);
       isdw = cvr_expf(-Stau);
     }
-    const float inv_k = 1.0f / (ka + kd);
-    if (P.phong && P.grad) {
-      float g[3];
-      grd.sample(x, y, z, g);
-      if (g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f) {
-        const v3 n = normalize3(mk(g[0], g[1], g[2]));
-        const v3 L = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-        const v3 Ve = normalize3(mk(eye.x - wp.x, eye.y - wp.y, eye.z - wp.z));
-        const v3 Hv = normalize3(mk(Ve.x + L.x, Ve.y + L.y, Ve.z + L.z));
-        const float dd = std::fmax(0.0f, dot3(n, L));
-        const float ds = std::fmax(0.0f, dot3(Hv, n));
-        const float pw = cvr_powf(ds, P.shininess);
-        // (1/(ka+kd)) * (L*IOcc*ka + IShadow*(L*kd*dot_diff)) + IShadow*(ks*Ispecular*pow) (:528-530)
-        for (int q = 0; q < 3; q++)
-          src[q] = inv_k * ((src[q] * iocc) * ka + isdw * ((src[q] * kd) * dd)) +
-                   isdw * ((ks * P.ispec[q]) * pw);
-      }
-    } else {
-      for (int q = 0; q < 3; q++) src[q] = inv_k * ((src[q] * iocc) * ka + (src[q] * isdw) * kd);
-    }
+    float g[3];
+    combine_sat(P, ka, kd, ks, iocc, isdw, wp, src, shading_gradient(P, x, y, z, g));
   };
   return shaded_march_rows(P, y0, y1, out_rgba, out_counts, nthreads, shade);
 }

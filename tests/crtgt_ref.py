@@ -9,24 +9,11 @@ oracle/Makefile's flags into tests/support/build/ and binds its function:
 from __future__ import annotations
 
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
 from oracle import oracle as O   # the module itself: its struct mirrors and _params helper
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "support", "crtgt_ref.cpp")
-LIB_PATH = os.path.join(HERE, "support", "build", "libcrtgt_ref.so")
-# oracle/Makefile's CXXFLAGS + ARCHFLAGS, exactly
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fopenmp",
-         "-march=x86-64-v3"]
-DEPS = [SRC, os.path.join(ROOT, "oracle", "cvr_oracle.cpp"),
-        os.path.join(ROOT, "oracle", "glsl_literal.cpp"), os.path.join(ROOT, "oracle", "oracle_types.h")]
-
-_lib = None
+from ref_build import build_and_load
 
 
 class GtRef(ctypes.Structure):
@@ -39,27 +26,14 @@ class GtRef(ctypes.Structure):
                 ("occ_rays", ctypes.c_void_p), ("sdw_rays", ctypes.c_void_p)]
 
 
-def build() -> str:
-    """Compile the reference (when missing or older than its sources)."""
-    if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in DEPS):
-        return LIB_PATH
-    os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
-    tmp = LIB_PATH + f".{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CXX", "g++"), *FLAGS, "-shared", "-o", tmp, SRC,
-                    os.path.join(ROOT, "oracle", "glsl_literal.cpp")], check=True)
-    os.replace(tmp, LIB_PATH)
-    return LIB_PATH
+def _bind(L):
+    P, I = ctypes.c_void_p, ctypes.c_int
+    L.gtref_render_rows.argtypes = [ctypes.POINTER(GtRef), I, I, P, P, I]
+    L.gtref_render_rows.restype = ctypes.c_uint64
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(build())
-        P, I = ctypes.c_void_p, ctypes.c_int
-        L.gtref_render_rows.argtypes = [ctypes.POINTER(GtRef), I, I, P, P, I]
-        L.gtref_render_rows.restype = ctypes.c_uint64
-        _lib = L
-    return _lib
+    return build_and_load("crtgt_ref", _bind)
 
 
 def half_rays(rays) -> np.ndarray:

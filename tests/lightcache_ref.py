@@ -10,50 +10,24 @@ flags into tests/support/build/ and binds its two functions:
 from __future__ import annotations
 
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
 from oracle import oracle as O   # the module itself: its struct mirrors and _params / _cone helpers
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "support", "lightcache_ref.cpp")
-LIB_PATH = os.path.join(HERE, "support", "build", "liblightcache_ref.so")
-# oracle/Makefile's CXXFLAGS + ARCHFLAGS, exactly
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fopenmp",
-         "-march=x86-64-v3"]
-DEPS = [SRC, os.path.join(ROOT, "oracle", "cvr_oracle.cpp"),
-        os.path.join(ROOT, "oracle", "glsl_literal.cpp"), os.path.join(ROOT, "oracle", "oracle_types.h")]
-
-_lib = None
+from ref_build import build_and_load
 
 
-def build() -> str:
-    """Compile the reference (when missing or older than its sources)."""
-    if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in DEPS):
-        return LIB_PATH
-    os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
-    tmp = LIB_PATH + f".{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CXX", "g++"), *FLAGS, "-shared", "-o", tmp, SRC,
-                    os.path.join(ROOT, "oracle", "glsl_literal.cpp")], check=True)
-    os.replace(tmp, LIB_PATH)
-    return LIB_PATH
+def _bind(L):
+    P, I = ctypes.c_void_p, ctypes.c_int
+    IP = ctypes.POINTER(ctypes.c_int)
+    L.lcref_dos_cache.argtypes = [ctypes.POINTER(O.OracleDos), IP, P, I]
+    L.lcref_dos_cache.restype = None
+    L.lcref_render_rows.argtypes = [ctypes.POINTER(O.OracleDos), P, IP, I, I, P, P, I]
+    L.lcref_render_rows.restype = ctypes.c_uint64
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(build())
-        P, I = ctypes.c_void_p, ctypes.c_int
-        IP = ctypes.POINTER(ctypes.c_int)
-        L.lcref_dos_cache.argtypes = [ctypes.POINTER(O.OracleDos), IP, P, I]
-        L.lcref_dos_cache.restype = None
-        L.lcref_render_rows.argtypes = [ctypes.POINTER(O.OracleDos), P, IP, I, I, P, P, I]
-        L.lcref_render_rows.restype = ctypes.c_uint64
-        _lib = L
-    return _lib
+    return build_and_load("lightcache_ref", _bind)
 
 
 def _dos(vol16, scale, tf_rgbt, ext_levels, camera, W, H, step, occ_tables, sdw_tables,

@@ -5,10 +5,11 @@
 //    the shaded renderers with ShadeSample's two bundles of secondary rays.
 //
 // The oracle is frozen, so this file includes its translation unit: Tex, tf_lookup,
-// the camera and slab code of shaded_march_rows and cvr_expf / cvr_powf live in
-// anonymous namespaces there and are the very functions the pinned oracles run.  New
-// here is only the text the ground-truth renderer adds to CVR-SPEC (DESIGN.md §5d′):
-// the per-ray frame, the secondary-ray loop, the shadow frames and the combine.
+// the camera and slab code of shaded_march_rows, ShadeSample's tail (combine_cones)
+// and cvr_expf / cvr_powf live in anonymous namespaces there and are the very
+// functions the pinned oracles run.  New here is only the text the ground-truth
+// renderer adds to CVR-SPEC (DESIGN.md §5d′): the per-ray frame, the secondary-ray
+// loop and the shadow frames.
 // Built with the oracle's flags (-ffp-contract=off: explicit fmaf only).
 #include "../../oracle/cvr_oracle.cpp"
 
@@ -74,14 +75,12 @@ extern "C" __attribute__((visibility("default"))) uint64_t gtref_render_rows(con
                                                                             float* out_rgba, uint32_t* out_counts,
                                                                             int nthreads) {
   const OracleRc1pass& P = Q->base;
-  const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
   const v3 G = mk((float)P.N[0] * P.scale[0], (float)P.N[1] * P.scale[1], (float)P.N[2] * P.scale[2]);
   const v3 light = mk(P.light[0], P.light[1], P.light[2]);
   // LightCamForward = -forward (crtgtrenderer.cpp:227), LightCamUp, LightCamRight
   const v3 lz = mk(-Q->light_forward[0], -Q->light_forward[1], -Q->light_forward[2]);
   const v3 lup = mk(Q->light_up[0], Q->light_up[1], Q->light_up[2]);
   const v3 lright = mk(Q->light_right[0], Q->light_right[1], Q->light_right[2]);
-  Tex grd{P.grad, {P.N[0], P.N[1], P.N[2]}, 3, P.filter_bits};
   const GtScene S{Tex{P.vol, {P.N[0], P.N[1], P.N[2]}, 1, P.filter_bits}, P.tf, P.tf_n, P.filter_bits, G,
                   mk((float)P.N[0] / G.x, (float)P.N[1] / G.y, (float)P.N[2] / G.z), Q->light_gap, Q->light_step};
   const float ka = Q->apply_occlusion ? P.ka : 0.0f;
@@ -97,6 +96,7 @@ extern "C" __attribute__((visibility("default"))) uint64_t gtref_render_rows(con
       iocc = S.cone(Q->occ_rays, Q->n_occ, Q->occ_distance, tx, v_right, v_up, normalize3(ncam));
     }
     if (Q->apply_shadow) {
+      // this shader's own frame, not the oracle's shadow_cone_frame (other axes, -forward, 30.0)
       v3 v_dir, v_up, v_right;
       bool on = true;
       if (Q->shadow_type == 2) {
@@ -109,24 +109,10 @@ extern "C" __attribute__((visibility("default"))) uint64_t gtref_render_rows(con
       }
       if (on) isdw = S.cone(Q->sdw_rays, Q->n_sdw, Q->sdw_distance, tx, v_right, v_up, v_dir);
     }
-    const float inv_k = 1.0f / (ka + kd);
-    if (P.phong && P.grad) {
-      float g[3];
-      grd.sample(x, y, z, g);
-      if (g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f) {
-        const v3 n = normalize3(mk(g[0], g[1], g[2]));
-        const v3 L = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-        const v3 Ve = normalize3(mk(eye.x - wp.x, eye.y - wp.y, eye.z - wp.z));
-        const v3 Hv = normalize3(mk(Ve.x + L.x, Ve.y + L.y, Ve.z + L.z));
-        const float dd = std::fmax(0.0f, dot3(n, L));
-        const float ds = std::fmax(0.0f, dot3(Hv, n));
-        const float diff = inv_k * (iocc * ka + (isdw * kd) * dd);
-        const float spec = (isdw * ks) * cvr_powf(ds, P.shininess);
-        for (int q = 0; q < 3; q++) src[q] = src[q] * diff + spec;
-      }
-    } else {
-      for (int q = 0; q < 3; q++) src[q] = inv_k * ((src[q] * iocc) * ka + (src[q] * isdw) * kd);
-    }
+    // ShadeSample (:254-302): the DOS combine with vec3(1) for the specular colour
+    // (P.ispec, set by crtgt_ref.py; fma(1, spec, x) rounds as x + spec)
+    float g[3];
+    combine_cones(P, ka, kd, ks, iocc, isdw, wp, src, shading_gradient(P, x, y, z, g));
   };
   return shaded_march_rows(P, y0, y1, out_rgba, out_counts, nthreads, shade);
 }

@@ -38,12 +38,8 @@ extern "C" __attribute__((visibility("default"))) void lcref_dos_cache(const Ora
   const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
   const v3 G = mk((float)P.N[0] * P.scale[0], (float)P.N[1] * P.scale[1], (float)P.N[2] * P.scale[2]);
   const v3 half = mk(G.x * 0.5f, G.y * 0.5f, G.z * 0.5f);
-  const v3 light = mk(P.light[0], P.light[1], P.light[2]);
-  const v3 lfwd = mk(Q->light_forward[0], Q->light_forward[1], Q->light_forward[2]);
-  const v3 lup = mk(Q->light_up[0], Q->light_up[1], Q->light_up[2]);
-  const v3 lright = mk(Q->light_right[0], Q->light_right[1], Q->light_right[2]);
+  const float spot_cos = dos_spot_cos(Q);
   const ExtVol E = make_ext(Q, G);
-  const float spot_cos = std::cos(3.14159265358979323846f * Q->spot_angle_deg / 180.0f);
   // VolumeScales * (VolumeDimensions / LightCacheDimensions) (:537)
   const v3 vs = mk(P.scale[0] * ((float)P.N[0] / (float)dims[0]), P.scale[1] * ((float)P.N[1] / (float)dims[1]),
                    P.scale[2] * ((float)P.N[2] / (float)dims[2]));
@@ -70,15 +66,7 @@ extern "C" __attribute__((visibility("default"))) void lcref_dos_cache(const Ora
         }
         if (Q->apply_shadow) {      // ShadowEvaluationKernel (:492-521)
           v3 k, u, v;
-          bool lit = true;
-          if (Q->shadow_type == 2) {
-            k = lfwd; v = lup; u = lright;
-          } else {
-            k = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-            u = normalize3(cross3(k, lright));
-            v = normalize3(cross3(k, u));
-            if (Q->shadow_type == 1 && dot3(k, lfwd) < spot_cos) lit = false;
-          }
+          const bool lit = shadow_cone_frame(Q, spot_cos, wp, k, u, v);
           // Cone1RayShadow(pos, k, v, u) is called as (pos, k, u, v): swapped
           idcs = lit ? cone_trace(E, Q->sdw, tx, k, v, u) : 0.0f;
         }
@@ -94,10 +82,7 @@ extern "C" __attribute__((visibility("default"))) uint64_t lcref_render_rows(
     const OracleDos* Q, const uint16_t* rg, const int dims[3], int y0, int y1, float* out_rgba,
     uint32_t* out_counts, int nthreads) {
   OracleRc1pass P = Q->base;
-  const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
   const v3 G = mk((float)P.N[0] * P.scale[0], (float)P.N[1] * P.scale[1], (float)P.N[2] * P.scale[2]);
-  const v3 light = mk(P.light[0], P.light[1], P.light[2]);
-  Tex grd{P.grad, {P.N[0], P.N[1], P.N[2]}, 3, P.filter_bits};
   const size_t nv = (size_t)dims[0] * dims[1] * dims[2];
   std::vector<float> cf(2 * nv);
   for (size_t i = 0; i < 2 * nv; i++) cf[i] = half_to_float(rg[i]);
@@ -113,24 +98,8 @@ extern "C" __attribute__((visibility("default"))) uint64_t lcref_render_rows(
     cache.sample(std::fmaf(tx.x, LoG.x, -0.5f), std::fmaf(tx.y, LoG.y, -0.5f), std::fmaf(tx.z, LoG.z, -0.5f), ia);
     const float iocc = Q->apply_occlusion ? ia[0] : 0.0f;
     const float isdw = Q->apply_shadow ? ia[1] : 0.0f;
-    const float inv_k = 1.0f / (ka + kd);
-    if (P.phong && P.grad) {
-      float g[3];
-      grd.sample(x, y, z, g);
-      if (g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f) {
-        const v3 n = normalize3(mk(g[0], g[1], g[2]));
-        const v3 L = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-        const v3 Ve = normalize3(mk(eye.x - wp.x, eye.y - wp.y, eye.z - wp.z));
-        const v3 Hv = normalize3(mk(Ve.x + L.x, Ve.y + L.y, Ve.z + L.z));
-        const float dd = std::fmax(0.0f, dot3(n, L));
-        const float ds = std::fmax(0.0f, dot3(Hv, n));
-        const float diff = inv_k * (iocc * ka + (isdw * kd) * dd);
-        const float spec = (isdw * ks) * cvr_powf(ds, P.shininess);
-        for (int q = 0; q < 3; q++) src[q] = std::fmaf(P.ispec[q], spec, src[q] * diff);
-      }
-    } else {
-      for (int q = 0; q < 3; q++) src[q] = inv_k * ((src[q] * iocc) * ka + (src[q] * isdw) * kd);
-    }
+    float g[3];
+    combine_cones(P, ka, kd, ks, iocc, isdw, wp, src, shading_gradient(P, x, y, z, g));
   };
   // `if (src.a > 0 && Shade)` (:312): with Shade off no sample is composited and no
   // ray terminates early, which is the shared march over a TF without opacity (its

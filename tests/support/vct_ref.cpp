@@ -166,10 +166,8 @@ extern "C" __attribute__((visibility("default"))) uint64_t vctref_render_rows(Vc
                                                                              float* out_rgba,
                                                                              uint32_t* out_counts, int nthreads) {
   const OracleRc1pass& P = Q->base;
-  const v3 eye = mk(P.eye[0], P.eye[1], P.eye[2]);
   const v3 G = mk((float)P.N[0] * P.scale[0], (float)P.N[1] * P.scale[1], (float)P.N[2] * P.scale[2]);
   const v3 light = mk(P.light[0], P.light[1], P.light[2]);
-  Tex grd{P.grad, {P.N[0], P.N[1], P.N[2]}, 3, P.filter_bits};
   VctScene S{Q, G, {}, P.filter_bits};
   S.off.assign(Q->nl + 1, 0);
   for (int L = 0; L < Q->nl; L++)
@@ -214,24 +212,9 @@ extern "C" __attribute__((visibility("default"))) uint64_t vctref_render_rows(Vc
   auto shade = [&](float* src, v3 tx, v3 wp, v3, float x, float y, float z) {
     float ivd = 0.0f;
     if (Q->apply_shadow) ivd = cone(tx, wp);
-    const float inv_k = 1.0f / (ka + kd);
-    if (P.phong && P.grad) {
-      float g[3];
-      grd.sample(x, y, z, g);
-      if (g[0] != 0.0f || g[1] != 0.0f || g[2] != 0.0f) {
-        const v3 n = normalize3(mk(g[0], g[1], g[2]));
-        const v3 L = normalize3(mk(light.x - wp.x, light.y - wp.y, light.z - wp.z));
-        const v3 Ve = normalize3(mk(eye.x - wp.x, eye.y - wp.y, eye.z - wp.z));
-        const v3 Hv = normalize3(mk(Ve.x + L.x, Ve.y + L.y, Ve.z + L.z));
-        const float dd = std::fmax(0.0f, dot3(n, L));
-        const float ds = std::fmax(0.0f, dot3(Hv, n));
-        const float pw = cvr_powf(ds, P.shininess);
-        for (int q = 0; q < 3; q++)
-          src[q] = inv_k * (src[q] * ka + ivd * ((src[q] * kd) * dd)) + ivd * ((ks * P.ispec[q]) * pw);
-      }
-    } else {
-      for (int q = 0; q < 3; q++) src[q] = inv_k * (src[q] * ka + (src[q] * ivd) * kd);
-    }
+    // ShadeSample (:146-189): the EBS tail without an occlusion term (L*ka is (L*1)*ka exactly)
+    float g[3];
+    combine_sat(P, ka, kd, ks, 1.0f, ivd, wp, src, shading_gradient(P, x, y, z, g));
   };
   const uint64_t total = shaded_march_rows(P, y0, y1, out_rgba, out_counts, nthreads, shade);
   for (int k = 0; k < 8; k++) Q->stats[k] = stats[k];

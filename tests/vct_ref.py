@@ -13,26 +13,14 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
-import subprocess
 
 import numpy as np
 
 from oracle import oracle as O   # the module itself: its struct mirrors and _params helper
+from ref_build import build_and_load
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "support", "vct_ref.cpp")
-LIB_PATH = os.path.join(HERE, "support", "build", "libvct_ref.so")
-# oracle/Makefile's CXXFLAGS + ARCHFLAGS, exactly
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fopenmp",
-         "-march=x86-64-v3"]
-DEPS = [SRC, os.path.join(ROOT, "oracle", "cvr_oracle.cpp"),
-        os.path.join(ROOT, "oracle", "glsl_literal.cpp"), os.path.join(ROOT, "oracle", "oracle_types.h")]
 MAX_LEVELS = 16
 STATS = ("cones", "cut", "full", "level0_only", "top_only", "pair_mask", "fetches")
-
-_lib = None
 
 
 class VctRef(ctypes.Structure):
@@ -46,31 +34,18 @@ class VctRef(ctypes.Structure):
                 ("samples", ctypes.c_int32), ("stats", ctypes.c_uint64 * 8)]
 
 
-def build() -> str:
-    """Compile the reference (when missing or older than its sources)."""
-    if os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in DEPS):
-        return LIB_PATH
-    os.makedirs(os.path.dirname(LIB_PATH), exist_ok=True)
-    tmp = LIB_PATH + f".{os.getpid()}.tmp"
-    subprocess.run([os.environ.get("CXX", "g++"), *FLAGS, "-shared", "-o", tmp, SRC,
-                    os.path.join(ROOT, "oracle", "glsl_literal.cpp")], check=True)
-    os.replace(tmp, LIB_PATH)
-    return LIB_PATH
+def _bind(L):
+    P, I = ctypes.c_void_p, ctypes.c_int
+    L.vctref_pyramid.argtypes = [P, I, I, I, P, P, P]
+    L.vctref_pyramid.restype = I
+    L.vctref_table.argtypes = [P, ctypes.c_double, P]
+    L.vctref_table.restype = I
+    L.vctref_render_rows.argtypes = [ctypes.POINTER(VctRef), I, I, P, P, I]
+    L.vctref_render_rows.restype = ctypes.c_uint64
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = ctypes.CDLL(build())
-        P, I = ctypes.c_void_p, ctypes.c_int
-        L.vctref_pyramid.argtypes = [P, I, I, I, P, P, P]
-        L.vctref_pyramid.restype = I
-        L.vctref_table.argtypes = [P, ctypes.c_double, P]
-        L.vctref_table.restype = I
-        L.vctref_render_rows.argtypes = [ctypes.POINTER(VctRef), I, I, P, P, I]
-        L.vctref_render_rows.restype = ctypes.c_uint64
-        _lib = L
-    return _lib
+    return build_and_load("vct_ref", _bind)
 
 
 def level_dims(shape):
