@@ -86,6 +86,25 @@ static cvr_status build_tf_table(const double* rgb_cp, int n_rgb, const double* 
   return CVR_OK;
 }
 
+// What hangs off what: the state derived from (volume, TF) that a new volume, a
+// new TF and the context's end drop, one line per struct of Ctx.  The pyramid and
+// the SAT outlive a TF change: each was built from a table of its own
+// (cvr_set_extinction_volume, cvr_set_extinction_sat, which also drop the light
+// cache).  The device has drained (QUIESCE) before any of this is freed.
+enum class Changed { kVolume, kTransferFunction, kDestroy };
+static void derived_drop(Ctx* c, Changed what) {
+  const bool volume_gone = what != Changed::kTransferFunction;
+  const bool tf_gone = what != Changed::kVolume;
+  const bool destroy = what == Changed::kDestroy;
+  skip_drop(c, volume_gone, tf_gone);
+  if (volume_gone) ext_drop(c);
+  if (volume_gone) sat_drop(c);
+  light_cache_drop(c, destroy);
+  if (destroy) crtgt_release(c); else crtgt_invalidate(c);
+  vct_drop(c, volume_gone);
+  if (volume_gone) iso_drop(c);
+}
+
 static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, int bpv, int w,
                                     int h, int d, const float scale[3]) {
   if (!src || (bpv != 1 && bpv != 2) || w < 1 || h < 1 || d < 1 || !scale)
@@ -100,7 +119,6 @@ static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, in
   free_dev(c->d_vox); c->vox_bytes = 0;
   free_dev(c->d_cells); c->cells_bytes = 0;
   free_dev(c->d_grad); c->grad_bytes = 0; c->grad_mode = 0;
-  c->iso_valid = 0;
   c->N[0] = w; c->N[1] = h; c->N[2] = d;
   for (int i = 0; i < 3; i++) c->scale[i] = scale[i];
   c->bpv = bpv;
@@ -114,23 +132,7 @@ static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, in
   for (int v = 0; v < nv; v++)
     lut[v] = to_half_bits((float)((double)v / (bpv == 1 ? (256.0 - 1.0) : (65536.0 - 1.0))));
   free_dev(c->d_lut);
-  free_dev(c->d_macro_minmax);
-  free_dev(c->d_occ);
-  c->mm_shift = -1;
-  c->occ_valid = 0;
-  c->cell_flags_valid = 0;   // the cells are rebuilt without flags
-  c->cell_flags_set = 0;
-  c->cell_flags_oom = 0;
-  free_dev(c->d_ext); c->ext_levels = 0;
-  free_dev(c->d_ext_cells);
-  free_dev(c->d_sat);
-  free_dev(c->d_sat_cells);
-  free_dev(c->d_sat_scratch);
-  c->sat_dims[0] = c->sat_dims[1] = c->sat_dims[2] = 0;
-  c->cone_valid = 0;
-  light_cache_drop(c);
-  crtgt_invalidate(c);
-  vct_drop(c, true);
+  derived_drop(c, Changed::kVolume);
   HIP_TRY(c, hipMalloc((void**)&c->d_lut, nv * sizeof(uint16_t)));
   uint16_t* d_lut = c->d_lut;
   hipError_t e = hipMemcpyAsync(d_lut, lut.data(), nv * sizeof(uint16_t), hipMemcpyHostToDevice,
@@ -298,25 +300,10 @@ void cvr_destroy(cvr_ctx* ctx) {
   free_dev(c->d_cells);
   free_dev(c->d_tf);
   free_dev(c->d_grad);
-  free_dev(c->d_iso_mm);
   free_dev(c->d_lut);
-  free_dev(c->d_macro_minmax);
-  free_dev(c->d_occ);
-  free_dev(c->d_tf_prefix);
-  free_dev(c->d_ext);
-  free_dev(c->d_ext_cells);
-  free_dev(c->d_ext_levels);
-  free_dev(c->d_sat);
-  free_dev(c->d_sat_cells);
-  free_dev(c->d_sat_scratch);
+  derived_drop(c, Changed::kDestroy);
   free_dev(c->d_shade);
   for (auto& J : c->flat) cvr::flat_release(J);
-  free_dev(c->d_cones);
-  delete[] c->cone_tab;
-  light_cache_drop(c);
-  crtgt_release(c);
-  vct_drop(c, true);
-  if (c->lc_ev) (void)hipEventDestroy(c->lc_ev);
   free_dev(c->d_total);
   free_dev(c->d_scratch);
   if (c->side) (void)hipStreamSynchronize(c->side);
@@ -373,7 +360,7 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
     return b;
   }
   return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
-         c->lc_bytes + c->gt.bytes + c->vct.bytes;
+         c->lc.bytes + c->gt.bytes + c->vct.bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {
@@ -418,9 +405,7 @@ cvr_status cvr_set_transfer_function(cvr_ctx* ctx, const float* rgbt, int n) {
     if (i % 4 == 3) amax = std::isfinite(q[i]) ? std::max(amax, q[i]) : NAN;
   }
   QUIESCE(c);   // frames in flight on any stream read the state replaced below
-  light_cache_drop(c);
-  crtgt_invalidate(c);
-  vct_drop(c, false);
+  derived_drop(c, Changed::kTransferFunction);
   if (n != c->tf_n) {
     free_dev(c->d_tf);
     HIP_TRY(c, hipMalloc((void**)&c->d_tf, (size_t)n * 16));
@@ -428,21 +413,7 @@ cvr_status cvr_set_transfer_function(cvr_ctx* ctx, const float* rgbt, int n) {
   }
   HIP_TRY(c, hipMemcpy(c->d_tf, q.data(), (size_t)n * 16, hipMemcpyHostToDevice));
   c->tf_max_alpha = amax;
-  // occupancy support: prefix[k] = #{padded entries j < k with alpha > 0}, where
-  // padded entry j is T[clamp(j - 1, 0, n - 1)] (j = 0 .. n + 1)
-  std::vector<int> prefix((size_t)n + 3, 0);
-  for (int j = 0; j < n + 2; j++) {
-    const float a = q[(size_t)std::min(std::max(j - 1, 0), n - 1) * 4 + 3];
-    prefix[(size_t)j + 1] = prefix[(size_t)j] + (a > 0.0f || a != a ? 1 : 0);
-  }
-  free_dev(c->d_tf_prefix);
-  HIP_TRY(c, hipMalloc((void**)&c->d_tf_prefix, prefix.size() * sizeof(int)));
-  HIP_TRY(c, hipMemcpy(c->d_tf_prefix, prefix.data(), prefix.size() * sizeof(int),
-                       hipMemcpyHostToDevice));
-  c->occ_valid = 0;
-  c->cell_flags_valid = 0;
-  c->cell_flags_oom = 0;
-  return CVR_OK;
+  return skip_set_tf(c, q.data(), n);
 }
 
 cvr_status cvr_set_gradient(cvr_ctx* ctx, int mode) {

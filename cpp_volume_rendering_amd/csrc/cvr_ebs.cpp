@@ -11,6 +11,18 @@ using namespace cvr;
 
 namespace cvr {
 
+// The whole SAT (a new volume, another grid, a failed build), or only the build's
+// double grid and / or the cell4 copy, which go while the SAT stays.
+void sat_drop(Ctx* c, int parts) {
+  Ctx::Sat& t = c->sat;
+  if (parts & kSatScratch) free_dev(t.d_scratch);
+  if (parts & kSatCells) free_dev(t.d_cells);
+  if (parts == kSatAll) {
+    free_dev(t.d_sat);
+    t.dims[0] = t.dims[1] = t.dims[2] = 0;
+  }
+}
+
 // dir_cone_max_distance = 0.75f * Dv (ebsrenderer.cpp:98-105, float arithmetic)
 // unless the caller gives one
 float ebs_max_distance(const Ctx* c, const cvr_ebs_params* p) {
@@ -36,14 +48,14 @@ cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_eb
     return fail(c, CVR_ERR_ARG, "%s: filter_bits %d needs sat_layout 0 (the cell4 copy)", who,
                 c->filter_bits);
   if (!c->d_cells || (o && !c->d_tf)) return fail(c, CVR_ERR_STATE, "%s: no volume or TF", who);
-  if (!c->d_sat) return fail(c, CVR_ERR_STATE, "%s: needs cvr_set_extinction_sat", who);
-  if (c->sat_layout == 0 && !c->d_sat_cells) {   // switched back to the cell4 copy: build it
-    const int w = c->sat_dims[0], h = c->sat_dims[1], d = c->sat_dims[2];
+  if (!c->sat.d_sat) return fail(c, CVR_ERR_STATE, "%s: needs cvr_set_extinction_sat", who);
+  if (c->sat_layout == 0 && !c->sat.d_cells) {   // switched back to the cell4 copy: build it
+    const int w = c->sat.dims[0], h = c->sat.dims[1], d = c->sat.dims[2];
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMalloc((void**)&c->d_sat_cells, cvr::sat_cells_float4s(w, h, d) * sizeof(float4)));
-    const hipError_t e = cvr::launch_sat_cells(*c, c->d_sat, c->d_sat_cells, c->stream);
+    HIP_TRY(c, hipMalloc((void**)&c->sat.d_cells, cvr::sat_cells_float4s(w, h, d) * sizeof(float4)));
+    const hipError_t e = cvr::launch_sat_cells(*c, c->sat.d_sat, c->sat.d_cells, c->stream);
     if (e != hipSuccess) {   // never leave an unbuilt copy behind for the next frame to read
-      free_dev(c->d_sat_cells);
+      sat_drop(c, kSatCells);
       return fail(c, CVR_ERR_HIP, "%s: cell4 SAT build: %s", who, hipGetErrorString(e));
     }
   }
@@ -78,10 +90,10 @@ cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_eb
   for (int i = 0; i < 3; i++) {
     Q.S[i] = c->scale[i];
     Q.inv_vs[i] = 1.0f / (Q.G[i] + Q.S[i] * 2.0f);        // inv_vol_scaled (:75)
-    Q.sat_dims[i] = c->sat_dims[i];
-    Q.sat_pz = (uint32_t)c->sat_dims[0] * (uint32_t)c->sat_dims[1];
-    Q.nsat[i] = (float)c->sat_dims[i];
-    Q.nsat_m1[i] = (float)(c->sat_dims[i] - 1);
+    Q.sat_dims[i] = c->sat.dims[i];
+    Q.sat_pz = (uint32_t)c->sat.dims[0] * (uint32_t)c->sat.dims[1];
+    Q.nsat[i] = (float)c->sat.dims[i];
+    Q.nsat_m1[i] = (float)(c->sat.dims[i] - 1);
     Q.min_sat[i] = Q.S[i] * 0.5f;                        // MinSATPosition (:66)
     Q.max_sat[i] = Q.G[i] + Q.S[i] * 1.5f;               // MaxSATPosition (:67)
     Q.lfwd[i] = p->light_forward[i];
@@ -136,61 +148,53 @@ cvr_status cvr_set_extinction_sat(cvr_ctx* ctx, const float* ext_lut, int lut_n)
   light_cache_drop(c);   // an EBS light cache holds this SAT's occlusion and shadow
   // Same grid as the last build (a TF change): rebuild into the existing buffers.
   // Freeing and re-allocating the ~30 GB of a 1024^3 SAT costs seconds.
-  const bool same = c->d_sat && c->sat_dims[0] == w && c->sat_dims[1] == h && c->sat_dims[2] == d;
-  if (!same) {
-    free_dev(c->d_sat);
-    free_dev(c->d_sat_cells);
-    free_dev(c->d_sat_scratch);
-    c->sat_dims[0] = c->sat_dims[1] = c->sat_dims[2] = 0;
-  }
+  const bool same = c->sat.d_sat && c->sat.dims[0] == w && c->sat.dims[1] == h && c->sat.dims[2] == d;
+  if (!same) sat_drop(c);
   float* d_lut = nullptr;
   hipError_t e = hipMalloc((void**)&d_lut, (size_t)nv * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(d_lut, ext_lut, (size_t)nv * sizeof(float), hipMemcpyHostToDevice);
   // the double recurrence's grid: kept with the SAT for rebuilds (sat_keep_scratch,
   // 8.6 GB at 1024^3) or allocated for this build only
-  if (e == hipSuccess && !c->d_sat_scratch) e = hipMalloc(&c->d_sat_scratch, cells * sizeof(double));
-  double* d_sd = (double*)c->d_sat_scratch;
+  if (e == hipSuccess && !c->sat.d_scratch) e = hipMalloc(&c->sat.d_scratch, cells * sizeof(double));
+  double* d_sd = (double*)c->sat.d_scratch;
   // the float SAT plus kSatPlainPadPlanes zero planes (the plain layout's clamped
   // +1 neighbours: cvr_sat_layout_check)
   const size_t pad_floats = cvr::sat_plain_floats(w, h, d) - cells;
-  if (e == hipSuccess && !same) e = hipMalloc((void**)&c->d_sat, cvr::sat_plain_floats(w, h, d) * sizeof(float));
-  if (e == hipSuccess && !same) e = hipMemsetAsync(c->d_sat + cells, 0, pad_floats * sizeof(float), c->stream);
+  if (e == hipSuccess && !same) e = hipMalloc((void**)&c->sat.d_sat, cvr::sat_plain_floats(w, h, d) * sizeof(float));
+  if (e == hipSuccess && !same) e = hipMemsetAsync(c->sat.d_sat + cells, 0, pad_floats * sizeof(float), c->stream);
   // GPU time of the two compute phases (option "sat_build_us"): the wall time of
   // this call also holds the allocations of ~50 GB at 1024^3
   hipEvent_t ev[4] = {};
   for (hipEvent_t& x : ev)
     if (e == hipSuccess) e = hipEventCreate(&x);
   if (e == hipSuccess) e = hipEventRecord(ev[0], c->stream);
-  if (e == hipSuccess) e = cvr::launch_sat_build(*c, d_lut, d_sd, c->d_sat, c->stream);
+  if (e == hipSuccess) e = cvr::launch_sat_build(*c, d_lut, d_sd, c->sat.d_sat, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[1], c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(d_lut);
-  if (!c->sat_keep_scratch) free_dev(c->d_sat_scratch);
+  if (!c->sat_keep_scratch) sat_drop(c, kSatScratch);
   // the cell4 copy only for the layout that reads it
-  if (e == hipSuccess && c->sat_layout == 0 && !c->d_sat_cells)
-    e = hipMalloc((void**)&c->d_sat_cells, cvr::sat_cells_float4s(w, h, d) * sizeof(float4));
+  if (e == hipSuccess && c->sat_layout == 0 && !c->sat.d_cells)
+    e = hipMalloc((void**)&c->sat.d_cells, cvr::sat_cells_float4s(w, h, d) * sizeof(float4));
   if (e == hipSuccess) e = hipEventRecord(ev[2], c->stream);
-  if (e == hipSuccess && c->sat_layout == 0) e = cvr::launch_sat_cells(*c, c->d_sat, c->d_sat_cells, c->stream);
+  if (e == hipSuccess && c->sat_layout == 0) e = cvr::launch_sat_cells(*c, c->sat.d_sat, c->sat.d_cells, c->stream);
   if (e == hipSuccess) e = hipEventRecord(ev[3], c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) {
     float a = 0.f, b = 0.f;
     if (hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess &&
         hipEventElapsedTime(&b, ev[2], ev[3]) == hipSuccess)
-      c->sat_build_us = (int)((a + b) * 1000.0f);
+      c->sat.build_us = (int)((a + b) * 1000.0f);
   }
-  if (e == hipSuccess && c->sat_layout == 1) free_dev(c->d_sat_cells);   // a copy from an earlier layout is stale now
+  if (e == hipSuccess && c->sat_layout == 1) sat_drop(c, kSatCells);   // a copy from an earlier layout is stale now
   for (hipEvent_t x : ev)
     if (x) (void)hipEventDestroy(x);
   if (e != hipSuccess) {
-    free_dev(c->d_sat);
-    free_dev(c->d_sat_cells);
-    free_dev(c->d_sat_scratch);
-    c->sat_dims[0] = c->sat_dims[1] = c->sat_dims[2] = 0;
+    sat_drop(c);
     return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,
                 "cvr_set_extinction_sat: %s", hipGetErrorString(e));
   }
-  c->sat_dims[0] = w; c->sat_dims[1] = h; c->sat_dims[2] = d;
+  c->sat.dims[0] = w; c->sat.dims[1] = h; c->sat.dims[2] = d;
   return CVR_OK;
 }
 
@@ -235,14 +239,14 @@ cvr_status cvr_copy_extinction_sat(cvr_ctx* ctx, float* out, size_t capacity, in
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (c && c->group) return cvr::group_call_root(c, [&](cvr_ctx* _m) { return cvr_copy_extinction_sat(_m, out, capacity, dims); });
   if (!c) return CVR_ERR_ARG;
-  if (!c->d_sat) return fail(c, CVR_ERR_STATE, "cvr_copy_extinction_sat: no SAT built");
-  if (dims) for (int i = 0; i < 3; i++) dims[i] = c->sat_dims[i];
+  if (!c->sat.d_sat) return fail(c, CVR_ERR_STATE, "cvr_copy_extinction_sat: no SAT built");
+  if (dims) for (int i = 0; i < 3; i++) dims[i] = c->sat.dims[i];
   if (!out) return CVR_OK;
-  const size_t n = (size_t)c->sat_dims[0] * c->sat_dims[1] * c->sat_dims[2];
+  const size_t n = (size_t)c->sat.dims[0] * c->sat.dims[1] * c->sat.dims[2];
   if (capacity < n) return fail(c, CVR_ERR_ARG, "cvr_copy_extinction_sat: buffer too small");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(out, c->d_sat, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(out, c->sat.d_sat, n * sizeof(float), hipMemcpyDeviceToHost));
   return CVR_OK;
 }
 

@@ -126,8 +126,21 @@ void default_light(cvr_light* l);
 // without them (cell_flags_or_off); any other error is returned.
 cvr_status enable_cell_skip(Ctx* c, Rc1passArgs& A, int level);
 
-// cvr_lightcache.cpp: a new volume, TF, extinction pyramid or SAT drops the cache
-void light_cache_drop(Ctx* c);
+// The drop functions of the context's derived state, one per struct of Ctx: each
+// frees the struct's device memory and resets its bookkeeping, after the caller
+// has drained the device (QUIESCE).  Who calls which: cvr_api.cpp derived_drop.
+// cvr_rc1pass.cpp: without the volume the macro cells go and the cells carry no
+// flags; without the TF its prefix counts go (skip_set_tf uploads the new TF's)
+void skip_drop(Ctx* c, bool volume_gone, bool tf_gone);
+cvr_status skip_set_tf(Ctx* c, const float* rgbt, int n);
+void ext_drop(Ctx* c);   // cvr_dos.cpp: the pyramid, its level table, the cone tables
+// cvr_ebs.cpp: the SAT, or only the parts of it that can go while it stays
+enum SatPart { kSatScratch = 1, kSatCells = 2, kSatAll = 7 };
+void sat_drop(Ctx* c, int parts = kSatAll);
+// cvr_lightcache.cpp: a new volume, TF, extinction pyramid or SAT drops the cache;
+// the context's end also destroys its event
+void light_cache_drop(Ctx* c, bool destroy = false);
+void iso_drop(Ctx* c);   // cvr_iso.cpp: the block table
 
 // cvr_crtgt.cpp: a new volume, TF or gradient ends the ground-truth frame in
 // progress; the context's end frees its state

@@ -340,22 +340,12 @@ struct Ctx {
   uint16_t* d_lut = nullptr;      // raw value -> R16F bits (GetNormalizedSample)
   // empty-space skipping (option "macro": log2 of the macro cell, 0 = off)
   int macro_shift = 3;
-  int mm_shift = -1;              // shift the macro min/max below was built for
-  int mdim[3] = {0, 0, 0};
-  uint32_t* d_macro_minmax = nullptr;
-  uint8_t* d_occ = nullptr;
-  int occ_valid = 0;              // occupancy matches the current volume, TF and shift
-  float occ_empty = 0.0f;         // fraction of empty macro cells
   int skip_min_pct = 15;          // skipping is compiled in when >= this % of cells are empty
-  int* d_tf_prefix = nullptr;     // count of padded TF entries with alpha > 0 before k
   // per-cell skip flags in the cells' sign bits (march_common.h cell_empty /
   // cell_skip_q; option "cell_skip": 0 off, 1 empty-sample flags, 2 flags + the
   // distance skip per lane, 3 (default) when every marching lane can, 4 by the
-  // lanes that can; raymarch.hip march_ray); rebuilt lazily after the volume or TF changes
+  // lanes that can; raymarch.hip march_ray)
   int cell_skip = 3;
-  int cell_flags_valid = 0;       // the cells' flags match the current TF
-  int cell_flags_set = 0;         // the cells carry flags (of some TF)
-  int cell_flags_oom = 0;         // the last flag build ran out of memory (retried after a volume / TF change)
   int debug_flags_oom = 0;        // tests (option "debug_cell_flags_oom"): the flag build reports OOM
   // transfer function (RGBA16F values as float)
   float* d_tf = nullptr;
@@ -425,59 +415,95 @@ struct Ctx {
   hipStream_t side = nullptr;      // high-priority stream for the order builds
   hipEvent_t ev_frame = nullptr;   // end of a frame's ray-march (the side stream waits on it)
   int num_cus = 0;
-  // extinction-coefficient mip volume (directional occlusion)
-  uint16_t* d_ext = nullptr;       // fp16 levels, concatenated (x-fastest)
-  uint4* d_ext_cells = nullptr;    // the same levels as cell8 (8 fp16 corners per texel)
-  ExtLevel* d_ext_levels = nullptr;  // [kMaxExtLevels] addressing of the levels
-  // extinction-based shading: the float SAT of (N+2) cells per axis
-  int sat_chunk = 32;                // z planes per SAT work item (option "sat_chunk")
-  int sat_build_us = 0;              // GPU time of the last SAT build (option "sat_build_us")
-  float* d_sat = nullptr;
-  float4* d_sat_cells = nullptr;   // the same SAT as cell4 texels (4 float corners of a plane, sat.hip)
-  int sat_layout = 0;              // option "sat_layout": the frame reads 0 = cell4 copy, 1 = the plain SAT
-  int sat_keep_scratch = 0;        // option "sat_keep_scratch": 1 keeps the double build grid for rebuilds
-  void* d_sat_scratch = nullptr;   // the double grid of the build (kept for rebuilds)
-  int sat_dims[3] = {0, 0, 0};
-  int ext_res[3] = {0, 0, 0};
-  int ext_levels = 0;
-  int ext_finite = 0;                // every TF opacity < 1: the pyramid's extinctions are finite
-  long long ext_off[kMaxExtLevels + 1] = {};
-  float ext_sigma0 = 1.0f;
-  // cone tables on the device (occlusion, shadow), rebuilt when their params change
-  float4* d_cones = nullptr;
-  cvr_cone_params cone_key[2] = {};
-  int cone_valid = 0;
-  cvr_cone_tables* cone_tab = nullptr;   // host copies [2]
-  // pre-illumination light cache (lightcache.hip): RG16F, 4 B per voxel
-  uint32_t* d_lcache = nullptr;
-  int lc_dims[3] = {0, 0, 0};
-  size_t lc_bytes = 0;
-  int lc_builds = 0;                 // computes so far (option "light_cache_builds", read-only)
-  // what the cache was computed from (cvr_render_dosct_preillum and
+  // options of the EBS SAT build: z planes per work item; the frame reads 0 = the cell4
+  // copy, 1 = the plain SAT; 1 keeps the double build grid for rebuilds
+  int sat_chunk = 32, sat_layout = 0, sat_keep_scratch = 0;
+  // State derived from (volume, TF): one struct per technique, each with one drop
+  // function (cvr_host.h); cvr_api.cpp derived_drop says who drops which.
+  // Empty-space skipping (cvr_rc1pass.cpp), from (volume, TF, option "macro"): the
+  // macro cells' min/max (of the volume, for mm_shift), the TF's prefix counts of
+  // entries with alpha > 0, the occupancy built of both (occ_empty: the empty
+  // fraction), and whether the density cells' sign bits carry skip flags (set), of
+  // the current TF (valid), or their build ran out of memory (oom: retried after a
+  // volume / TF change).  Occupancy and flags are rebuilt lazily by the frames.
+  struct Skip {
+    uint32_t* d_macro_minmax = nullptr;
+    uint8_t* d_occ = nullptr;
+    int* d_tf_prefix = nullptr;
+    int mm_shift = -1, mdim[3] = {0, 0, 0}, occ_valid = 0;
+    float occ_empty = 0.0f;
+    int flags_valid = 0, flags_set = 0, flags_oom = 0;
+  } skip;
+  // Directional occlusion (cvr_dos.cpp), from (volume, the RGBA TF and sigma0 of
+  // cvr_set_extinction_volume): the extinction pyramid as fp16 levels (x fastest,
+  // concatenated at `off`) and as cell8 texels, its level table [kMaxExtLevels]
+  // for the cone fetches, finite (every TF opacity < 1: no infinite extinction),
+  // and the cone tables (occlusion, shadow) of cone_key on the host and the
+  // device, rebuilt when a frame's cone parameters differ.
+  struct Ext {
+    uint16_t* d_ext = nullptr;
+    uint4* d_cells = nullptr;
+    ExtLevel* d_levels = nullptr;
+    int res[3] = {0, 0, 0}, levels = 0, finite = 0;
+    long long off[kMaxExtLevels + 1] = {};
+    float sigma0 = 1.0f;
+    float4* d_cones = nullptr;
+    cvr_cone_params cone_key[2] = {};
+    int cone_valid = 0;
+    cvr_cone_tables cone_tab[2] = {};
+  } ext;
+  // Extinction-based shading (cvr_ebs.cpp), from (volume, the extinction LUT of
+  // cvr_set_extinction_sat): the float SAT of (N + 2) cells per axis, its cell4
+  // copy (4 float corners of a plane per texel, sat.hip; only while sat_layout 0
+  // reads it), the double grid of the build (only with sat_keep_scratch) and the
+  // GPU time of the last build.
+  struct Sat {
+    float* d_sat = nullptr;
+    float4* d_cells = nullptr;
+    void* d_scratch = nullptr;
+    int dims[3] = {0, 0, 0}, build_us = 0;
+  } sat;
+  // What a light cache was computed from (cvr_render_dosct_preillum and
   // cvr_render_extbsd_preillum skip the compute when nothing of it changed);
   // invalid after cvr_set_light_cache.  Compared as bytes: 4-byte members only.
+  // kind: the producer, 0 DOS cones, 1 EBS SAT; the other producer's part and the
+  // parameters of a term that is switched off stay zero.
   struct LightCacheKey {
-    int valid = 0;
-    int kind = 0;                      // the producer: 0 DOS cones, 1 EBS SAT
-    int dims[3] = {0, 0, 0};
+    int valid = 0, kind = 0, dims[3] = {0, 0, 0};
     int apply_occlusion = 0, apply_shadow = 0, shadow_type = 0, filter_bits = 0;
-    cvr_cone_params cone[2] = {};      // DOS
-    cvr_light light = {};              // DOS; EBS: position (type 0) or forward (type 1) only
-    float eye[3] = {0, 0, 0}, cam_up[3] = {0, 0, 0};   // DOS, compared only with occlusion on
-    // EBS: the AO parameters (occlusion on) and the shadow chain's (shadow on)
-    int ebs_shells = 0;
-    float ebs_radius = 0, ebs_angle = 0, ebs_interval = 0, ebs_initial = 0, ebs_weight = 0,
-          ebs_max_distance = 0;
-  } lc_key;
-  // frames that read the cache since it was last written: on one stream (a later
-  // write on that stream is ordered behind them) or on several (the write drains
-  // the device first)
-  hipStream_t lc_reader = nullptr;
-  int lc_readers = 0;                // 0 none, 1 lc_reader only, 2 several streams
-  // the last compute: its stream and end event (a frame on another stream waits for it)
-  hipEvent_t lc_ev = nullptr;
-  hipStream_t lc_writer = nullptr;
-  bool lc_written = false;
+    struct Dos {
+      cvr_cone_params cone[2] = {};
+      cvr_light light = {};
+      float eye[3] = {0, 0, 0}, cam_up[3] = {0, 0, 0};   // with occlusion on
+    } dos;
+    struct Ebs {
+      int shells = 0;
+      float radius = 0, angle = 0, interval = 0, initial = 0, weight = 0, max_distance = 0;
+      float light[3] = {0, 0, 0};      // the position (shadow type 0) or the forward vector (1)
+    } ebs;
+  };
+  // Pre-illumination (cvr_lightcache.cpp), from `key` plus the volume, the TF and
+  // the producer's pyramid or SAT: the RG16F cache (4 B per voxel), and who reads
+  // and wrote it.  readers: frames that read the cache since it was last written,
+  // 0 none, 1 on `reader` only (a later write on that stream is ordered behind
+  // them), 2 on several streams (the write drains the device first).  written: the
+  // last compute ran on `writer` and ended at `ev` (a frame on another stream
+  // waits for it).  builds: computes so far.
+  struct LightCache {
+    uint32_t* d_cache = nullptr;
+    int dims[3] = {0, 0, 0};
+    size_t bytes = 0;
+    LightCacheKey key;
+    hipStream_t reader = nullptr, writer = nullptr;
+    hipEvent_t ev = nullptr;
+    int readers = 0, builds = 0;
+    bool written = false;
+  } lc;
+  // Isosurface block table (cvr_iso.cpp), from (volume, nb): float2 min/max per block.
+  struct Iso {
+    float2* d_mm = nullptr;
+    int nb[3] = {0, 0, 0}, valid = 0;
+  } iso;
   // ground-truth cone ray-caster (cvr_crtgt.cpp): the progressive frame between
   // cvr_crtgt_begin and its cvr_crtgt_advance calls
   struct Crtgt {
@@ -518,10 +544,6 @@ struct Ctx {
   // another stream than the previous user waits for that frame (counters_guard)
   hipStream_t counters_stream = nullptr;
   hipEvent_t ev_counters = nullptr;
-  // isosurface block table (float2 min/max per block), built for iso_nb
-  float2* d_iso_mm = nullptr;
-  int iso_nb[3] = {0, 0, 0};
-  int iso_valid = 0;               // matches the current volume and iso_nb
   // multi-GPU gather (cvr_comm.cpp): RCCL communicator, its stream and events
   void* comm = nullptr;
   int split_streams = 1;           // option "split_streams": render streams the caller rotates

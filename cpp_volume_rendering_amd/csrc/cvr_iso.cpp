@@ -10,12 +10,19 @@
 
 using namespace cvr;
 
+// The block table goes with the volume (and with another block count).
+void cvr::iso_drop(Ctx* c) {
+  free_dev(c->iso.d_mm);
+  c->iso.nb[0] = c->iso.nb[1] = c->iso.nb[2] = 0;
+  c->iso.valid = 0;
+}
+
 // The block table for nb: raw extremes on the GPU, normalised here exactly as
 // ComputeBlocksFromVolume stores them (v / 255 or v / 65535 in double, pushed
 // into a float vector; empty blocks keep numeric_limits<float>::max / lowest).
 static cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]) {
-  if (c->iso_valid && c->d_iso_mm && c->iso_nb[0] == nb[0] && c->iso_nb[1] == nb[1] &&
-      c->iso_nb[2] == nb[2])
+  if (c->iso.valid && c->iso.d_mm && c->iso.nb[0] == nb[0] && c->iso.nb[1] == nb[1] &&
+      c->iso.nb[2] == nb[2])
     return CVR_OK;
   const size_t n = (size_t)nb[0] * nb[1] * nb[2];
   HIP_TRY(c, hipSetDevice(c->device));
@@ -38,11 +45,11 @@ static cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]) {
   }
   // frames still running on any render stream may read the old table
   HIP_TRY(c, hipDeviceSynchronize());
-  if (c->d_iso_mm && (c->iso_nb[0] * c->iso_nb[1] * c->iso_nb[2]) != (int)n) free_dev(c->d_iso_mm);
-  if (!c->d_iso_mm) HIP_TRY(c, hipMalloc((void**)&c->d_iso_mm, n * sizeof(float2)));
-  HIP_TRY(c, hipMemcpy(c->d_iso_mm, mm.data(), n * sizeof(float2), hipMemcpyHostToDevice));
-  for (int i = 0; i < 3; i++) c->iso_nb[i] = nb[i];
-  c->iso_valid = 1;
+  if (c->iso.d_mm && (c->iso.nb[0] * c->iso.nb[1] * c->iso.nb[2]) != (int)n) iso_drop(c);
+  if (!c->iso.d_mm) HIP_TRY(c, hipMalloc((void**)&c->iso.d_mm, n * sizeof(float2)));
+  HIP_TRY(c, hipMemcpy(c->iso.d_mm, mm.data(), n * sizeof(float2), hipMemcpyHostToDevice));
+  for (int i = 0; i < 3; i++) c->iso.nb[i] = nb[i];
+  c->iso.valid = 1;
   return CVR_OK;
 }
 
@@ -84,7 +91,7 @@ cvr_status cvr_iso_block_ranges(cvr_ctx* ctx, const int num_blocks[3], float* ou
   if (st != CVR_OK) return st;
   const size_t n = (size_t)num_blocks[0] * num_blocks[1] * num_blocks[2];
   std::vector<float2> mm(n);
-  HIP_TRY(c, hipMemcpy(mm.data(), c->d_iso_mm, n * sizeof(float2), hipMemcpyDeviceToHost));
+  HIP_TRY(c, hipMemcpy(mm.data(), c->iso.d_mm, n * sizeof(float2), hipMemcpyDeviceToHost));
   for (size_t i = 0; i < n; i++) { out_min[i] = mm[i].x; out_max[i] = mm[i].y; }
   return CVR_OK;
 }
@@ -143,7 +150,7 @@ cvr_status cvr_render_iso(cvr_ctx* ctx, const cvr_frame* f, const cvr_iso_params
     Q.inv_g[i] = 1.0f / Q.G[i];
   }
   for (int i = 0; i < 4; i++) Q.color[i] = p->color[i];
-  const float2* mm = p->variant != 2 ? c->d_iso_mm : nullptr;
+  const float2* mm = p->variant != 2 ? c->iso.d_mm : nullptr;
   const int variant = p->variant;
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long*,
                                                 unsigned long long* ts, hipStream_t st2) {

@@ -13,13 +13,15 @@ namespace cvr {
 
 // The pre-illumination light cache goes with the state it was computed from: a
 // new volume, TF, extinction pyramid or SAT drops it (after the device has drained).
-void light_cache_drop(Ctx* c) {
-  free_dev(c->d_lcache);
-  c->lc_bytes = 0;
-  c->lc_dims[0] = c->lc_dims[1] = c->lc_dims[2] = 0;
-  c->lc_key.valid = 0;
-  c->lc_readers = 0;
-  c->lc_written = false;
+void light_cache_drop(Ctx* c, bool destroy) {
+  Ctx::LightCache& l = c->lc;
+  free_dev(l.d_cache);
+  l.bytes = 0;
+  l.dims[0] = l.dims[1] = l.dims[2] = 0;
+  l.key.valid = 0;
+  l.readers = 0;
+  l.written = false;
+  if (destroy && l.ev) (void)hipEventDestroy(l.ev);
 }
 
 }  // namespace cvr
@@ -35,24 +37,24 @@ static cvr_status light_cache_check_dims(Ctx* c, const char* who, const int dims
 // it on this stream are ordered before the write; frames on other streams, or an
 // earlier write on another stream, are not, so the device drains first.
 static cvr_status light_cache_write_begin(Ctx* c) {
-  const bool foreign_reader = c->lc_readers == 2 || (c->lc_readers == 1 && c->lc_reader != c->stream);
-  const bool foreign_writer = c->lc_written && c->lc_writer != c->stream;
+  const bool foreign_reader = c->lc.readers == 2 || (c->lc.readers == 1 && c->lc.reader != c->stream);
+  const bool foreign_writer = c->lc.written && c->lc.writer != c->stream;
   if (foreign_reader || foreign_writer) QUIESCE(c);
-  c->lc_readers = 0;
-  c->lc_written = false;
+  c->lc.readers = 0;
+  c->lc.written = false;
   return CVR_OK;
 }
 
 // The cache buffer for `dims` (kept when the size is unchanged).
 static cvr_status light_cache_reserve(Ctx* c, const int dims[3]) {
   const size_t bytes = (size_t)dims[0] * dims[1] * dims[2] * 4;
-  if (!c->d_lcache || bytes != c->lc_bytes) {
+  if (!c->lc.d_cache || bytes != c->lc.bytes) {
     QUIESCE(c);   // frames in flight on any stream may read the buffer freed below
     light_cache_drop(c);
-    HIP_TRY(c, hipMalloc((void**)&c->d_lcache, bytes));
-    c->lc_bytes = bytes;
+    HIP_TRY(c, hipMalloc((void**)&c->lc.d_cache, bytes));
+    c->lc.bytes = bytes;
   }
-  for (int i = 0; i < 3; i++) c->lc_dims[i] = dims[i];
+  for (int i = 0; i < 3; i++) c->lc.dims[i] = dims[i];
   return CVR_OK;
 }
 
@@ -84,14 +86,14 @@ static void light_cache_key(const Ctx* c, const cvr_frame* f, const cvr_dos_para
   k.shadow_type = p->shadow_type;
   k.filter_bits = c->filter_bits;
   // a cone or a light that is switched off does not reach the cache
-  if (k.apply_occlusion) k.cone[0] = cp[0];
+  if (k.apply_occlusion) k.dos.cone[0] = cp[0];
   if (k.apply_shadow) {
-    k.cone[1] = cp[1];
-    k.light = p->light;
+    k.dos.cone[1] = cp[1];
+    k.dos.light = p->light;
   }
   if (k.apply_occlusion) {
-    for (int i = 0; i < 3; i++) k.eye[i] = f->camera.eye[i];
-    eye_cam_up(f, k.cam_up);
+    for (int i = 0; i < 3; i++) k.dos.eye[i] = f->camera.eye[i];
+    eye_cam_up(f, k.dos.cam_up);
   }
 }
 
@@ -106,27 +108,24 @@ static void ebs_light_cache_key(const Ctx* c, const cvr_ebs_params* p, const int
   k.filter_bits = c->filter_bits;
   // a term that is switched off does not reach the cache; the camera never does
   if (k.apply_occlusion) {
-    k.ebs_shells = p->occlusion_shells;
-    k.ebs_radius = p->occlusion_radius;
+    k.ebs.shells = p->occlusion_shells;
+    k.ebs.radius = p->occlusion_radius;
   }
   if (k.apply_shadow) {
     k.shadow_type = p->shadow_type;
-    k.ebs_angle = p->shadow_cone_angle_deg;
-    k.ebs_interval = p->shadow_sample_interval;
-    k.ebs_initial = p->shadow_initial_step;
-    k.ebs_weight = p->shadow_ui_weight;
-    k.ebs_max_distance = ebs_max_distance(c, p);
-    for (int i = 0; i < 3; i++) {
-      if (p->shadow_type == 0) k.light.position[i] = p->light_pos[i];
-      else k.light.forward[i] = p->light_forward[i];
-    }
+    k.ebs.angle = p->shadow_cone_angle_deg;
+    k.ebs.interval = p->shadow_sample_interval;
+    k.ebs.initial = p->shadow_initial_step;
+    k.ebs.weight = p->shadow_ui_weight;
+    k.ebs.max_distance = ebs_max_distance(c, p);
+    for (int i = 0; i < 3; i++) k.ebs.light[i] = p->shadow_type == 0 ? p->light_pos[i] : p->light_forward[i];
   }
 }
 
 // The context's cache was computed from exactly `key`: the *_preillum renders skip
 // the compute.
 static bool light_cache_fresh(const Ctx* c, const Ctx::LightCacheKey& key) {
-  return c->d_lcache && c->lc_key.valid && std::memcmp(&key, &c->lc_key, sizeof(key)) == 0;
+  return c->lc.d_cache && c->lc.key.valid && std::memcmp(&key, &c->lc.key, sizeof(key)) == 0;
 }
 
 // What the two PreComputeLightCache dispatches share, after the producer has
@@ -146,14 +145,14 @@ static cvr_status light_cache_compute(Ctx* c, const char* who, const int dims[3]
     // VolumeScales * (VolumeDimensions / LightCacheDimensions), float (:537)
     P.vs[i] = c->scale[i] * ((float)c->N[i] / (float)dims[i]);
   }
-  c->lc_key.valid = 0;
+  c->lc.key.valid = 0;
   HIP_TRY(c, launch(P));
-  if (!c->lc_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lc_ev, hipEventDisableTiming));
-  HIP_TRY(c, hipEventRecord(c->lc_ev, c->stream));
-  c->lc_written = true;
-  c->lc_writer = c->stream;
-  c->lc_builds++;
-  c->lc_key = key;
+  if (!c->lc.ev) HIP_TRY(c, hipEventCreateWithFlags(&c->lc.ev, hipEventDisableTiming));
+  HIP_TRY(c, hipEventRecord(c->lc.ev, c->stream));
+  c->lc.written = true;
+  c->lc.writer = c->stream;
+  c->lc.builds++;
+  c->lc.key = key;
   return CVR_OK;
 }
 
@@ -171,7 +170,7 @@ static cvr_status dos_light_cache_compute(Ctx* c, const char* who, const cvr_fra
   light_cache_key(c, f, p, cp, dims, key);
   return light_cache_compute(c, who, dims, [&](cvr::LightCacheArgs& P) {
     eye_cam_up(f, P.cam_up);
-    return cvr::launch_light_cache(Q, P, c->d_ext_cells, c->d_lcache, c->stream);
+    return cvr::launch_light_cache(Q, P, c->ext.d_cells, c->lc.d_cache, c->stream);
   }, key);
 }
 
@@ -188,7 +187,7 @@ static cvr_status ebs_light_cache_compute(Ctx* c, const char* who, const cvr_ebs
   Ctx::LightCacheKey key;
   ebs_light_cache_key(c, p, dims, key);
   return light_cache_compute(c, who, dims, [&](cvr::LightCacheArgs& P) {
-    return cvr::launch_ebs_light_cache(*c, Q, P, c->d_lcache, c->stream);
+    return cvr::launch_ebs_light_cache(*c, Q, P, c->lc.d_cache, c->stream);
   }, key);
 }
 
@@ -203,23 +202,23 @@ static cvr_status preillum_march(Ctx* c, const char* who, const cvr_frame* f, co
   cvr_cone_params cp[2];
   const cvr_status st = dos_prepare(c, who, f, p, o, false, Q, ntiles, npix, cp);
   if (st != CVR_OK) return st;
-  if (!c->d_lcache)
+  if (!c->lc.d_cache)
     return fail(c, CVR_ERR_STATE, "%s: no light cache (cvr_compute_light_cache_dosct / "
                                   "cvr_compute_light_cache_extbsd / cvr_set_light_cache)", who);
   cvr::LightCacheView V{};
-  V.rg = c->d_lcache;
+  V.rg = c->lc.d_cache;
   for (int i = 0; i < 3; i++) {
-    V.d[i] = c->lc_dims[i];
-    V.s[i] = (float)c->lc_dims[i] / Q.G[i];   // L / G, rounded once
-    V.m[i] = (float)(c->lc_dims[i] - 1);
+    V.d[i] = c->lc.dims[i];
+    V.s[i] = (float)c->lc.dims[i] / Q.G[i];   // L / G, rounded once
+    V.m[i] = (float)(c->lc.dims[i] - 1);
   }
   // a cache written on another stream: this frame waits for that write
-  if (c->lc_written && c->lc_writer != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->lc_ev, 0));
-  if (c->lc_readers == 0) {
-    c->lc_readers = 1;
-    c->lc_reader = c->stream;
-  } else if (c->lc_reader != c->stream) {
-    c->lc_readers = 2;
+  if (c->lc.written && c->lc.writer != c->stream) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->lc.ev, 0));
+  if (c->lc.readers == 0) {
+    c->lc.readers = 1;
+    c->lc.reader = c->stream;
+  } else if (c->lc.reader != c->stream) {
+    c->lc.readers = 2;
   }
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t st) {
@@ -253,11 +252,11 @@ cvr_status cvr_set_light_cache(cvr_ctx* ctx, const uint16_t* rg_half, const int 
   cvr_status st = light_cache_check_dims(c, "cvr_set_light_cache", dims);
   if (st != CVR_OK) return st;
   QUIESCE(c);   // frames in flight on any stream read the cache replaced below
-  c->lc_readers = 0;
-  c->lc_written = false;
+  c->lc.readers = 0;
+  c->lc.written = false;
   if ((st = light_cache_reserve(c, dims)) != CVR_OK) return st;
-  c->lc_key.valid = 0;   // not this library's compute: cvr_render_*_preillum recompute
-  HIP_TRY(c, hipMemcpy(c->d_lcache, rg_half, c->lc_bytes, hipMemcpyHostToDevice));
+  c->lc.key.valid = 0;   // not this library's compute: cvr_render_*_preillum recompute
+  HIP_TRY(c, hipMemcpy(c->lc.d_cache, rg_half, c->lc.bytes, hipMemcpyHostToDevice));
   return CVR_OK;
 }
 
@@ -265,16 +264,16 @@ cvr_status cvr_copy_light_cache(cvr_ctx* ctx, uint16_t* out, size_t capacity, in
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
   if (!c) return CVR_ERR_ARG;
   NO_GROUP(c, "cvr_copy_light_cache");
-  if (!c->d_lcache) return fail(c, CVR_ERR_STATE, "cvr_copy_light_cache: no light cache");
+  if (!c->lc.d_cache) return fail(c, CVR_ERR_STATE, "cvr_copy_light_cache: no light cache");
   if (dims)
-    for (int i = 0; i < 3; i++) dims[i] = c->lc_dims[i];
+    for (int i = 0; i < 3; i++) dims[i] = c->lc.dims[i];
   if (!out) return CVR_OK;
-  if (capacity < c->lc_bytes / 2)
-    return fail(c, CVR_ERR_ARG, "cvr_copy_light_cache: need %zu halfs", c->lc_bytes / 2);
+  if (capacity < c->lc.bytes / 2)
+    return fail(c, CVR_ERR_ARG, "cvr_copy_light_cache: need %zu halfs", c->lc.bytes / 2);
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (c->lc_written && c->lc_writer != c->stream) HIP_TRY(c, hipEventSynchronize(c->lc_ev));
-  HIP_TRY(c, hipMemcpy(out, c->d_lcache, c->lc_bytes, hipMemcpyDeviceToHost));
+  if (c->lc.written && c->lc.writer != c->stream) HIP_TRY(c, hipEventSynchronize(c->lc.ev));
+  HIP_TRY(c, hipMemcpy(out, c->lc.d_cache, c->lc.bytes, hipMemcpyDeviceToHost));
   return CVR_OK;
 }
 

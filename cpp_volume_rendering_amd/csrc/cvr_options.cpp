@@ -48,17 +48,17 @@ const Option kOptions[] = {
     {"sat_chunk", &Ctx::sat_chunk, nullptr, 1, 64, nullptr, nullptr, nullptr},
     {"sat_layout", &Ctx::sat_layout, nullptr, 0, 1, nullptr, "0 (cell4 copy) or 1 (the plain float SAT)",
      [](Ctx* c, int& value) {
-       if (value == 1 && c->d_sat_cells) {   // the copy is not needed any more (17 GiB at 1024^3)
+       if (value == 1 && c->sat.d_cells) {   // the copy is not needed any more (17 GiB at 1024^3)
          QUIESCE(c);
-         free_dev(c->d_sat_cells);
+         sat_drop(c, kSatCells);
        }
        return CVR_OK;
      }},
     {"sat_keep_scratch", &Ctx::sat_keep_scratch, nullptr, 0, 1, nullptr, nullptr,
      [](Ctx* c, int& value) {
-       if (!value && c->d_sat_scratch) {
+       if (!value && c->sat.d_scratch) {
          QUIESCE(c);
-         free_dev(c->d_sat_scratch);
+         sat_drop(c, kSatScratch);
        }
        return CVR_OK;
      }},
@@ -91,7 +91,7 @@ const Option kOptions[] = {
     {"macro", &Ctx::macro_shift, nullptr, 0, 6, [](int v) { return v != 1; },
      "0 (no empty-space skipping) or 2..6",
      [](Ctx* c, int&) {
-       c->occ_valid = 0;
+       c->skip.occ_valid = 0;
        return CVR_OK;
      }},
     {"cell_skip", &Ctx::cell_skip, nullptr, 0, 4, nullptr,
@@ -133,13 +133,13 @@ const Option kOptions[] = {
        return CVR_OK;
      }},
     // read-only
-    {"cell_flags_active", nullptr, [](const Ctx* c) { return (int)(c->cell_flags_valid && !c->cell_flags_oom); },
+    {"cell_flags_active", nullptr, [](const Ctx* c) { return (int)(c->skip.flags_valid && !c->skip.flags_oom); },
      1, 0, nullptr, nullptr, nullptr},
-    {"cell_flags_valid", &Ctx::cell_flags_valid, nullptr, 1, 0, nullptr, nullptr, nullptr},
-    {"sat_build_us", &Ctx::sat_build_us, nullptr, 1, 0, nullptr, nullptr, nullptr},
+    {"cell_flags_valid", nullptr, [](const Ctx* c) { return c->skip.flags_valid; }, 1, 0, nullptr, nullptr, nullptr},
+    {"sat_build_us", nullptr, [](const Ctx* c) { return c->sat.build_us; }, 1, 0, nullptr, nullptr, nullptr},
     // empty macro cells (after a render)
     {"occ_empty_permille", nullptr,
-     [](const Ctx* c) { return c->occ_valid ? (int)(c->occ_empty * 1000.0f + 0.5f) : -1; },
+     [](const Ctx* c) { return c->skip.occ_valid ? (int)(c->skip.occ_empty * 1000.0f + 0.5f) : -1; },
      1, 0, nullptr, nullptr, nullptr},
     // the context stream's job-list capacity
     {"flat_cap_kjobs", nullptr,
@@ -149,7 +149,7 @@ const Option kOptions[] = {
        return 0;
      },
      1, 0, nullptr, nullptr, nullptr},
-    {"light_cache_builds", &Ctx::lc_builds, nullptr, 1, 0, nullptr, nullptr, nullptr},
+    {"light_cache_builds", nullptr, [](const Ctx* c) { return c->lc.builds; }, 1, 0, nullptr, nullptr, nullptr},
     {"vct_pyramid_builds", nullptr, [](const Ctx* c) { return c->vct.builds; }, 1, 0, nullptr, nullptr, nullptr},
 };
 

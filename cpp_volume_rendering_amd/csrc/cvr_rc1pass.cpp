@@ -39,34 +39,69 @@ cvr_status ensure_scratch(Ctx* c, size_t bytes) {
   return CVR_OK;
 }
 
+// The macro cells were built for one volume and one macro size.
+static void skip_drop_macro(Ctx::Skip& k) {
+  free_dev(k.d_macro_minmax);
+  free_dev(k.d_occ);
+  k.mm_shift = -1;
+  k.occ_valid = 0;
+}
+
+void skip_drop(Ctx* c, bool volume_gone, bool tf_gone) {
+  Ctx::Skip& k = c->skip;
+  k.occ_valid = 0;
+  k.flags_valid = 0;
+  k.flags_oom = 0;
+  if (volume_gone) {
+    skip_drop_macro(k);
+    k.flags_set = 0;   // the cells are rebuilt without flags
+  }
+  if (tf_gone) free_dev(k.d_tf_prefix);
+}
+
+// Occupancy support for the TF just set (RGBA16F-rounded, n entries): prefix[k] =
+// #{padded entries j < k with alpha > 0}, where padded entry j is
+// T[clamp(j - 1, 0, n - 1)] (j = 0 .. n + 1).  The old TF's went with skip_drop.
+cvr_status skip_set_tf(Ctx* c, const float* rgbt, int n) {
+  std::vector<int> prefix((size_t)n + 3, 0);
+  for (int j = 0; j < n + 2; j++) {
+    const float a = rgbt[(size_t)std::min(std::max(j - 1, 0), n - 1) * 4 + 3];
+    prefix[(size_t)j + 1] = prefix[(size_t)j] + (a > 0.0f || a != a ? 1 : 0);
+  }
+  HIP_TRY(c, hipMalloc((void**)&c->skip.d_tf_prefix, prefix.size() * sizeof(int)));
+  HIP_TRY(c, hipMemcpy(c->skip.d_tf_prefix, prefix.data(), prefix.size() * sizeof(int),
+                       hipMemcpyHostToDevice));
+  return CVR_OK;
+}
+
 // Occupancy of the macro cells for the current volume, TF and macro size
 // (rebuilt lazily after any of them changes; on the context stream).
 cvr_status ensure_occupancy(Ctx* c) {
-  if (c->occ_valid) return CVR_OK;
-  if (!c->d_lut || !c->d_tf_prefix) return fail(c, CVR_ERR_STATE, "occupancy: no volume or TF");
+  Ctx::Skip& k = c->skip;
+  if (k.occ_valid) return CVR_OK;
+  if (!c->d_lut || !k.d_tf_prefix) return fail(c, CVR_ERR_STATE, "occupancy: no volume or TF");
   QUIESCE(c);   // frames in flight on other streams may still read d_occ
   const int sh = c->macro_shift;
-  if (c->mm_shift != sh) {
-    for (int i = 0; i < 3; i++) c->mdim[i] = ((c->N[i] - 1) >> sh) + 1;
-    const size_t nm = (size_t)c->mdim[0] * c->mdim[1] * c->mdim[2];
-    free_dev(c->d_macro_minmax);
-    free_dev(c->d_occ);
-    HIP_TRY(c, hipMalloc((void**)&c->d_macro_minmax, nm * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->d_occ, nm));
-    HIP_TRY(c, cvr::launch_macro_minmax(*c, sh, c->mdim, c->d_macro_minmax, c->stream));
-    c->mm_shift = sh;
+  if (k.mm_shift != sh) {
+    skip_drop_macro(k);
+    for (int i = 0; i < 3; i++) k.mdim[i] = ((c->N[i] - 1) >> sh) + 1;
+    const size_t nm = (size_t)k.mdim[0] * k.mdim[1] * k.mdim[2];
+    HIP_TRY(c, hipMalloc((void**)&k.d_macro_minmax, nm * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc((void**)&k.d_occ, nm));
+    HIP_TRY(c, cvr::launch_macro_minmax(*c, sh, k.mdim, k.d_macro_minmax, c->stream));
+    k.mm_shift = sh;
   }
-  const int nm = c->mdim[0] * c->mdim[1] * c->mdim[2];
+  const int nm = k.mdim[0] * k.mdim[1] * k.mdim[2];
   if (!c->d_total) HIP_TRY(c, hipMalloc((void**)&c->d_total, sizeof(unsigned long long)));
   unsigned int* d_n = reinterpret_cast<unsigned int*>(c->d_total);
   HIP_TRY(c, hipMemsetAsync(d_n, 0, sizeof(unsigned int), c->stream));
-  HIP_TRY(c, cvr::launch_occupancy(c->d_macro_minmax, nm, c->d_lut, c->d_tf_prefix, c->tf_n,
-                                   c->d_occ, d_n, c->stream));
+  HIP_TRY(c, cvr::launch_occupancy(k.d_macro_minmax, nm, c->d_lut, k.d_tf_prefix, c->tf_n,
+                                   k.d_occ, d_n, c->stream));
   unsigned int n_empty = 0;
   HIP_TRY(c, hipMemcpyAsync(&n_empty, d_n, sizeof(n_empty), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->occ_empty = (float)n_empty / (float)nm;
-  c->occ_valid = 1;
+  k.occ_empty = (float)n_empty / (float)nm;
+  k.occ_valid = 1;
   return CVR_OK;
 }
 
@@ -75,8 +110,8 @@ cvr_status ensure_occupancy(Ctx* c) {
 // streams may still read the cells' old flags, so the device drains first (a
 // TF change is rare); the two scratch bytes per cell are freed after the build.
 cvr_status ensure_cell_flags(Ctx* c) {
-  if (c->cell_flags_valid) return CVR_OK;
-  if (!c->d_cells || !c->d_tf_prefix) return fail(c, CVR_ERR_STATE, "cell flags: no volume or TF");
+  if (c->skip.flags_valid) return CVR_OK;
+  if (!c->d_cells || !c->skip.d_tf_prefix) return fail(c, CVR_ERR_STATE, "cell flags: no volume or TF");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipDeviceSynchronize());
   const size_t n = cvr::cell_count(c->cells);
@@ -90,8 +125,8 @@ cvr_status ensure_cell_flags(Ctx* c) {
   if (e != hipSuccess)
     return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "cell flags: %s",
                 hipGetErrorString(e));
-  c->cell_flags_valid = 1;
-  c->cell_flags_set = 1;
+  c->skip.flags_valid = 1;
+  c->skip.flags_set = 1;
   return CVR_OK;
 }
 
@@ -103,11 +138,11 @@ cvr_status ensure_cell_flags(Ctx* c) {
 // succeeds, so the OOM message is not left in cvr_last_error.  Any other error is
 // returned.
 cvr_status cell_flags_or_off(Ctx* c) {
-  if (c->cell_flags_oom && !c->cell_flags_valid) return CVR_ERR_OOM;
+  if (c->skip.flags_oom && !c->skip.flags_valid) return CVR_ERR_OOM;
   const cvr_status st = ensure_cell_flags(c);
   if (st == CVR_ERR_OOM) {
     (void)hipGetLastError();   // clear the failed allocation's error
-    c->cell_flags_oom = 1;
+    c->skip.flags_oom = 1;
     c->err.clear();
   }
   return st;
@@ -276,9 +311,9 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
     if (st != CVR_OK) return st;
     // the skip path costs the march registers and a probe: worth it only
     // with enough empty space (the Marschner-Lobb headline field has ~4 %)
-    if (c->occ_empty * 100.0f >= (float)c->skip_min_pct) {
-      A.occ = c->d_occ;
-      for (int i = 0; i < 3; i++) A.mdim[i] = c->mdim[i];
+    if (c->skip.occ_empty * 100.0f >= (float)c->skip_min_pct) {
+      A.occ = c->skip.d_occ;
+      for (int i = 0; i < 3; i++) A.mdim[i] = c->skip.mdim[i];
       A.mshift = c->macro_shift;
     }
   }

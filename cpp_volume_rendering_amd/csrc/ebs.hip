@@ -78,11 +78,11 @@ hipError_t launch_ebs(const Ctx& c, const EbsArgs& q, float4* out, uint32_t* sam
                       unsigned long long* shade, unsigned long long* tile_samples, hipStream_t s) {
   if (q.a.filter_bits == 8)   // GL texture-unit weights (CVR-SPEC-8): the cell4 copy only
     return c.sat_layout == 1 ? hipErrorInvalidValue
-                             : launch_ebs_layout<SatFB<SatCell4, 8>>(c, q, c.d_sat_cells, out, samples,
+                             : launch_ebs_layout<SatFB<SatCell4, 8>>(c, q, c.sat.d_cells, out, samples,
                                                                      shade, tile_samples, s);
   if (c.sat_layout == 1)
-    return launch_ebs_layout<SatPlain>(c, q, c.d_sat, out, samples, shade, tile_samples, s);
-  return launch_ebs_layout<SatCell4>(c, q, c.d_sat_cells, out, samples, shade, tile_samples, s);
+    return launch_ebs_layout<SatPlain>(c, q, c.sat.d_sat, out, samples, shade, tile_samples, s);
+  return launch_ebs_layout<SatCell4>(c, q, c.sat.d_cells, out, samples, shade, tile_samples, s);
 }
 
 }  // namespace cvr

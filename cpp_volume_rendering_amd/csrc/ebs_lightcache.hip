@@ -77,9 +77,9 @@ hipError_t launch_ebs_light_cache(const Ctx& c, const EbsArgs& q, const LightCac
   if (q.a.filter_bits == 8)   // GL texture-unit weights (CVR-SPEC-8): the cell4 copy only, as launch_ebs
     return c.sat_layout == 1
                ? hipErrorInvalidValue
-               : launch_ebs_light_cache_layout<SatFB<SatCell4, 8>>(q, P, grid, c.d_sat_cells, out, s);
-  if (c.sat_layout == 1) return launch_ebs_light_cache_layout<SatPlain>(q, P, grid, c.d_sat, out, s);
-  return launch_ebs_light_cache_layout<SatCell4>(q, P, grid, c.d_sat_cells, out, s);
+               : launch_ebs_light_cache_layout<SatFB<SatCell4, 8>>(q, P, grid, c.sat.d_cells, out, s);
+  if (c.sat_layout == 1) return launch_ebs_light_cache_layout<SatPlain>(q, P, grid, c.sat.d_sat, out, s);
+  return launch_ebs_light_cache_layout<SatCell4>(q, P, grid, c.sat.d_cells, out, s);
 }
 
 }  // namespace cvr

@@ -399,7 +399,7 @@ hipError_t launch_cell_flags(const Ctx& c, bool clear, uint8_t* t0, uint8_t* t1,
     hipLaunchKernelGGL(fill_u8_kernel, grid, dim3(bs), 0, s, t0, n, (uint8_t)0);
   } else {
     hipLaunchKernelGGL(cell_empty_kernel, grid, dim3(bs), 0, s, (const uint4*)cells, n,
-                       c.d_tf_prefix, c.tf_n, t0);
+                       c.skip.d_tf_prefix, c.tf_n, t0);
     for (int axis = 0; axis < 3; axis++) {
       hipLaunchKernelGGL(cell_dist_axis_kernel, grid, dim3(bs), 0, s, (const uint8_t*)t0, t1, n,
                          c.cells.cx, c.cells.cy, c.cells.cz, axis);
