@@ -68,8 +68,9 @@ __global__ void __launch_bounds__(64) crtgt_init_kernel(Rc1passArgs A, CrtgtStat
   if (threadIdx.x == 0 && n) atomicAdd(&S.ctr[1], n);
 }
 
-// Round step 1.  The loop of :417-473 for at most k iterations per pixel, with the
-// arithmetic of the shaded marches (shaded_march.h shaded_jobs_kernel).
+// Round step 1.  The loop of :417-473 for at most k iterations per pixel: the step of
+// the shaded marches (shaded_march.h march_fetch, march_classify, march_composite),
+// without a gate, resumed from the state.
 template <int FB, bool PHONG>
 __global__ void __launch_bounds__(64)
 crtgt_march_kernel(CrtgtArgs Q, const uint4* __restrict__ cells, const uint4* __restrict__ grad,
@@ -91,40 +92,20 @@ crtgt_march_kernel(CrtgtArgs Q, const uint4* __restrict__ cells, const uint4* __
     s = S.s[pix];
     dst_a = S.dst[pix].w;
   }
-  const float step = A.step, fn = (float)A.tf_n;
-  constexpr int F4 = PHONG ? 3 : 2;
+  const float fn = (float)A.tf_n;
   uint32_t cnt = 0, n = 0;
   for (int it = 0; it < k; it++) {   // wave-uniform
     if (__ballot(active) == 0) break;
     bool pushed = false;
     if (active) {
-      const float h = fminf(step, r.D - s);
-      const float tt = fmaf(h, 0.5f, s);
-      const float x = fmaf(r.dt.x, tt, r.o.x), y = fmaf(r.dt.y, tt, r.o.y), z = fmaf(r.dt.z, tt, r.o.z);
-      SamplePos sp = wave_in_box ? sample_pos(x, y, z, A) : sample_pos_clamped(x, y, z, A);
-      if (FB) quantise_weights<FB>(sp);
-      const float4 sc = classify<FB>(tfp, fn, trilerp_cell(cells[sp.idx], sp.ax, sp.ay, sp.az));
+      MarchFetch f = march_fetch(A, cells, r, s, wave_in_box);
+      const float4 sc = march_classify<FB>(f, tfp, fn);
       cnt++;
-      if (sc.w > 0.0f) {
-        const float a = 1.0f - cvr_expf(-(sc.w * h));
-        const float om = 1.0f - dst_a;
-        const f3 tx = vmad(r.dir, tt, r.tpos);        // s_tex_pos, box at [0, G]
-        float4* jp = S.jobs + ((size_t)pix * K + n) * F4;
-        jp[0] = make_float4(tx.x, tx.y, tx.z, a);
-        jp[1] = make_float4(sc.x, sc.y, sc.z, om);
-        if (PHONG) {
-          const f3 g = sample_gradient_cell(grad, sp);
-          jp[2] = make_float4(g.x, g.y, g.z, 0.0f);
-        }
-        dst_a = fmaf(om, a, dst_a);
+      march_composite<PHONG>(r, f, sc, true, grad, dst_a, s, active, [&](const ShadeJob& job) {
+        job.store<PHONG>(S.jobs + ((size_t)pix * K + n) * ShadeJob::f4(PHONG));
         n++;
         pushed = true;
-        if (dst_a > 0.99f) active = false;
-      }
-      if (active) {
-        s = s + h;
-        active = s < r.D;
-      }
+      });
     }
     // the iteration's jobs, appended to the round's list (their order in it is free:
     // every job has its own slot, and the fold reads the slots per pixel)
@@ -230,17 +211,16 @@ crtgt_shade_kernel(CrtgtArgs Q, const uint4* __restrict__ cells, const float4* _
   const int lane = threadIdx.x & 63;
   const unsigned long long njobs = S.ctr[0];
   const unsigned long long nwaves = (unsigned long long)gridDim.x * 4;
-  constexpr int F4 = PHONG ? 3 : 2;
   for (unsigned long long j = (unsigned long long)blockIdx.x * 4 + (threadIdx.x >> 6); j < njobs; j += nwaves) {
     const uint32_t slot = S.list[j];
-    float4* jp = S.jobs + (size_t)slot * F4;
-    const float4 q0 = jp[0], q1 = jp[1];
+    float4* jp = S.jobs + (size_t)slot * ShadeJob::f4(PHONG);
+    const ShadeJob job = ShadeJob::head(jp);
     const uint32_t pix = slot / K;
     const int py = (int)(pix / (uint32_t)A.W), px = (int)(pix - (uint32_t)py * (uint32_t)A.W);
     Ray r;
     (void)ray_setup(A, px, py, r);
     const f3 cam = r.cam;
-    const f3 tx{q0.x, q0.y, q0.z};
+    const f3 tx = job.tx;
     const f3 wp{tx.x - A.half_grid[0], tx.y - A.half_grid[1], tx.z - A.half_grid[2]};
     float iocc = 0.0f, isdw = 0.0f;
     if (Q.apply_occlusion) {
@@ -274,14 +254,12 @@ crtgt_shade_kernel(CrtgtArgs Q, const uint4* __restrict__ cells, const float4* _
         isdw = cone_rays<FB>(Q, cells, tau, Q.sdw_rays, Q.n_sdw, Q.sdw_distance, tx, v_right, v_up, v_dir, lane);
     }
     f3 g;
-    if (PHONG) {
-      const float4 q2 = jp[2];
-      g = f3{q2.x, q2.y, q2.z};
-    }
+    if (PHONG) g = ShadeJob::grad(jp);
     // ShadeSample (:254-302): the DOS renderer's combine with vec3(1) for the specular
     // colour (A.ispec, set by the host)
-    const f3 c = combine_cones(A, Q.ka, Q.kd, Q.ks, iocc, isdw, wp, f3{q1.x, q1.y, q1.z}, PHONG ? &g : nullptr);
-    if (lane == 0) jp[1] = make_float4(c.x * q0.w, c.y * q0.w, c.z * q0.w, q1.w);
+    const f3 c = combine_cones(A, Q.ka, Q.kd, Q.ks, iocc, isdw, wp, job.rgb, PHONG ? &g : nullptr);
+    // the record's {rgb, w} becomes {shaded rgb * a, 1 - dst.a}: what the fold reads
+    if (lane == 0) jp[ShadeJob::kRgbW] = make_float4(c.x * job.a, c.y * job.a, c.z * job.a, job.w);
   }
 }
 
@@ -295,7 +273,7 @@ __global__ void __launch_bounds__(64) crtgt_fold_kernel(Rc1passArgs A, CrtgtStat
   if (n == 0) return;
   float4 dst = S.dst[pix];
   for (uint32_t j = 0; j < n; j++) {
-    const float4 v = S.jobs[((size_t)pix * K + j) * f4 + 1];
+    const float4 v = S.jobs[((size_t)pix * K + j) * f4 + ShadeJob::kRgbW];
     dst.x = fmaf(v.w, v.x, dst.x);
     dst.y = fmaf(v.w, v.y, dst.y);
     dst.z = fmaf(v.w, v.z, dst.z);
@@ -321,23 +299,20 @@ hipError_t launch_round_fb(const Ctx& c, const CrtgtArgs& q, const CrtgtState& s
   const uint4* cells = (const uint4*)c.d_cells;
   const uint4* grad = (const uint4*)c.d_grad;
   const float4* tf = (const float4*)c.d_tf;
-  if (q.phong)
-    hipLaunchKernelGGL((crtgt_march_kernel<FB, true>), dim3(nt), dim3(64), lds, s, q, cells, grad, tf, st, k);
-  else
-    hipLaunchKernelGGL((crtgt_march_kernel<FB, false>), dim3(nt), dim3(64), lds, s, q, cells, grad, tf, st, k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
   // 8 workgroups of 4 waves per CU, no more than the round can hold jobs
   const size_t cap = (size_t)q.a.W * q.a.H * K;
   const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)std::max(c.num_cus, 1) * 8, (cap + 3) / 4));
   const size_t lds_tau = (size_t)(q.a.tf_n + 2) * sizeof(float);
-  if (q.phong)
-    hipLaunchKernelGGL((crtgt_shade_kernel<FB, true>), dim3(grid), dim3(256), lds_tau, s, q, cells, tf, st);
-  else
-    hipLaunchKernelGGL((crtgt_shade_kernel<FB, false>), dim3(grid), dim3(256), lds_tau, s, q, cells, tf, st);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(crtgt_fold_kernel, dim3(nt), dim3(64), 0, s, q.a, st, q.phong ? 3 : 2);
-  return hipGetLastError();
+  return with_phong(q.phong, [&](auto P) {
+    constexpr bool PHONG = decltype(P)::value;
+    hipLaunchKernelGGL((crtgt_march_kernel<FB, PHONG>), dim3(nt), dim3(64), lds, s, q, cells, grad, tf, st, k);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((crtgt_shade_kernel<FB, PHONG>), dim3(grid), dim3(256), lds_tau, s, q, cells, tf, st);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(crtgt_fold_kernel, dim3(nt), dim3(64), 0, s, q.a, st, ShadeJob::f4(PHONG));
+    return hipGetLastError();
+  });
 }
 
 }  // namespace

@@ -1,7 +1,13 @@
 // shaded_march.h — the single-pass march of the shaded renderers (rc1pdosct,
-// rc1pextbsd) with their per-sample shading deferred into full-wave batches.
+// rc1pextbsd, rc1pvctsg and the ground truth rc1pcrtgt) with their per-sample
+// shading deferred: into full-wave batches (shaded_march_kernel), into one job
+// list per frame (flat shading, below) or into one per launch round (crtgt.hip).
+// All of them take a sample with the same step: march_fetch, march_classify and
+// march_composite, which the job-list marches call and the per-wave kernel
+// writes out (see there), and the lists hold the same record (ShadeJob).
 //
-// ray_bbox_marching.comp:658-734 and ebs_ray_bbox_marching.comp:552-625 march
+// ray_bbox_marching.comp:658-734, ebs_ray_bbox_marching.comp:552-625, the main
+// of vct_ray_bbox_marching.comp and gt_ray_marching.comp:417-473 march
 // exactly as rc1pass does and, for every sample with alpha > 0, call an
 // expensive ShadeSample (cone tracing / SAT boxes: 10^2..10^3 fetches).  The
 // opacity of a sample, and with it the ERT break and the sample count, does not
@@ -64,6 +70,129 @@ struct ShaderGate<SH, std::void_t<decltype(&SH::gate)>> {
 #define CVR_SHADED_COLGROUP 4
 #endif
 
+// ---------------------------------------------------------------------------
+// One shading job: what a march hands to its shader for a sample with alpha > 0.
+// Stored as 2 float4 (3 with Phong): {tx, a}, {rgb, w}, {g, 0}.  w is 1 - dst.a
+// before the sample, as march_composite leaves it; the flat pipeline, whose fold
+// rebuilds dst.a from the alphas, stores the pixel's slot (int bits) there.
+// ---------------------------------------------------------------------------
+struct ShadeJob {
+  f3 tx;      // tx_pos, box at [0, G]
+  float a;    // the sample's alpha
+  f3 rgb;     // TF colour
+  float w;
+  f3 g;       // gradient sample (Phong only)
+
+  // float offsets in a stored record, and the float4 that holds {rgb, w}
+  static constexpr int kTx = 0, kA = 3, kRgb = 4, kW = 7, kG = 8;
+  static constexpr int kRgbW = kRgb / 4;
+  __host__ __device__ static constexpr int f4(bool phong) { return phong ? 3 : 2; }
+
+  template <bool PHONG>
+  __device__ __forceinline__ void store(float4* jp) const {
+    jp[0] = make_float4(tx.x, tx.y, tx.z, a);
+    jp[kRgbW] = make_float4(rgb.x, rgb.y, rgb.z, w);
+    if (PHONG) jp[2] = make_float4(g.x, g.y, g.z, 0.0f);
+  }
+  // the record without its gradient, and the gradient (two reads: a shader that
+  // needs the gradient only in its combine loads it after the traces)
+  __device__ static __forceinline__ ShadeJob head(const float4* jp) {
+    const float4 q0 = jp[0], q1 = jp[kRgbW];
+    ShadeJob j;
+    j.tx = f3{q0.x, q0.y, q0.z};
+    j.a = q0.w;
+    j.rgb = f3{q1.x, q1.y, q1.z};
+    j.w = q1.w;
+    return j;
+  }
+  __device__ static __forceinline__ f3 grad(const float4* jp) {
+    const float4 q2 = jp[2];
+    return f3{q2.x, q2.y, q2.z};
+  }
+};
+
+// ---------------------------------------------------------------------------
+// One march step, in the three pieces its callers need apart (the jobs kernel
+// votes on the raw cells between the first two, and counts the sample before the
+// third).  CVR-SPEC arithmetic: the operand order of every operation here is the
+// oracle's.
+// ---------------------------------------------------------------------------
+struct MarchFetch {
+  float h, tt;     // the step's length and its midpoint's ray parameter
+  SamplePos sp;
+  uint4 raw;       // the sample's cell
+};
+
+__device__ __forceinline__ MarchFetch march_fetch(const Rc1passArgs& A, const uint4* __restrict__ cells,
+                                                  const Ray& r, float s, bool wave_in_box) {
+  MarchFetch f;
+  f.h = fminf(A.step, r.D - s);
+  f.tt = fmaf(f.h, 0.5f, s);
+  const float x = fmaf(r.dt.x, f.tt, r.o.x), y = fmaf(r.dt.y, f.tt, r.o.y), z = fmaf(r.dt.z, f.tt, r.o.z);
+  f.sp = wave_in_box ? sample_pos(x, y, z, A) : sample_pos_clamped(x, y, z, A);
+  f.raw = cells[f.sp.idx];
+  return f;
+}
+
+// The TF's {rgb, tau} at the sample.  filter_bits quantises the weights in place:
+// the gradient fetch of march_composite takes the same ones.
+template <int FB>
+__device__ __forceinline__ float4 march_classify(MarchFetch& f, const float4* __restrict__ tfp, float fn) {
+  if (FB) quantise_weights<FB>(f.sp);
+  return classify<FB>(tfp, fn, trilerp_cell(f.raw, f.sp.ax, f.sp.ay, f.sp.az));
+}
+
+// Composites the sample: if it is a job (tau > 0 and the shader's gate), on_job
+// takes it and dst_a advances at once (it does not depend on the shading); the
+// ray then ends at dst_a > 0.99 (ERT) or at D, or steps on.
+// (on_job runs inside the job's own branch: a job handed out to a second `if`
+// at the call site stays live across the branches, 8 to 15 VGPRs.)
+template <bool PHONG, class OnJob>
+__device__ __forceinline__ void march_composite(const Ray& r, const MarchFetch& f, float4 sc, bool gate,
+                                                const uint4* __restrict__ grad, float& dst_a, float& s,
+                                                bool& active, OnJob&& on_job) {
+  if (sc.w > 0.0f && gate) {
+    ShadeJob job;
+    job.tx = vmad(r.dir, f.tt, r.tpos);
+    job.rgb = f3{sc.x, sc.y, sc.z};
+    job.a = 1.0f - cvr_expf(-(sc.w * f.h));
+    job.w = 1.0f - dst_a;
+    if (PHONG) job.g = sample_gradient_cell(grad, f.sp);
+    dst_a = fmaf(job.w, job.a, dst_a);
+    on_job(job);
+    if (dst_a > 0.99f) active = false;
+  }
+  if (active) {
+    s = s + f.h;
+    active = s < r.D;
+  }
+}
+
+// The tail of a march: the pixel's sample count, the tile's, and the wave's jobs
+// (njobs: this lane's share) into the roofline's counter.
+__device__ __forceinline__ void store_march_counts(const Rc1passArgs& A, bool inside, long long oidx, int t,
+                                                   int lane, uint32_t cnt, uint32_t njobs,
+                                                   uint32_t* __restrict__ samples,
+                                                   unsigned long long* __restrict__ tile_samples,
+                                                   unsigned long long* __restrict__ shade_ctr) {
+  if ((inside || A.packed) && samples) samples[oidx] = cnt;
+  if (tile_samples) {
+    const unsigned long long v = wave_sum(cnt);
+    if (lane == 0) tile_samples[t] = v;
+  }
+  if (shade_ctr) {   // measurement only
+    const unsigned long long sa = wave_sum(njobs);
+    if (lane == 0) atomicAdd(&shade_ctr[0], sa);
+  }
+}
+
+// f(std::true_type) or f(std::false_type): the runtime Phong switch as the
+// kernels' template argument.
+template <class F>
+inline auto with_phong(bool phong, F&& f) {
+  return phong ? f(std::true_type{}) : f(std::false_type{});
+}
+
 // One wave = one 8x8 tile.
 template <class SH, bool PHONG>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(SH::kMinWavesPerEU)))
@@ -121,6 +250,9 @@ shaded_march_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
       if (__ballot(can) == 0) break;
       bool pushed = false;
       if (can) {
+        // The step of march_fetch / march_classify / march_composite, written out: through
+        // the helpers the DOS kernel's scratch rises from 12 to 28 B per lane and its
+        // time by about half a percent.  A change to the step lands there and here.
         const float h = fminf(step, r.D - s);
         const float tt = fmaf(h, 0.5f, s);
         const float x = fmaf(r.dt.x, tt, r.o.x), y = fmaf(r.dt.y, tt, r.o.y),
@@ -199,18 +331,11 @@ shaded_march_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
     __syncthreads();
   }
 
-  if (inside || A.packed) {
-    store_rgba(out, oidx, dst, A.out_half);
-    if (samples) samples[oidx] = cnt;
-  }
-  if (tile_samples) {
-    const unsigned long long v = wave_sum(cnt);
-    if (lane == 0) tile_samples[t] = v;
-  }
+  if (inside || A.packed) store_rgba(out, oidx, dst, A.out_half);
+  store_march_counts(A, inside, oidx, t, lane, cnt, nshade, samples, tile_samples, shade_ctr);
   if (shade_ctr) {   // measurement only (secondary-fetch count of the roofline)
-    const unsigned long long sa = wave_sum(nshade), sl = wave_sum(nlit), sf = wave_sum(nfetch);
+    const unsigned long long sl = wave_sum(nlit), sf = wave_sum(nfetch);
     if (lane == 0) {
-      atomicAdd(&shade_ctr[0], sa);
       atomicAdd(&shade_ctr[1], sl);
       atomicAdd(&shade_ctr[2], sf);
     }
@@ -280,49 +405,27 @@ shaded_jobs_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
   for (;;) {   // one sample per live lane per round (wave-uniform loop)
     if (__ballot(active) == 0) break;
     bool pushed = false;
-    float4 q0, q1, q2;
-    float h = 0.0f, tt = 0.0f;
-    SamplePos sp;
-    uint4 raw;
+    ShadeJob job;
+    MarchFetch f;
     bool empty = true;
     if (active) {
-      h = fminf(step, r.D - s);
-      tt = fmaf(h, 0.5f, s);
-      const float x = fmaf(r.dt.x, tt, r.o.x), y = fmaf(r.dt.y, tt, r.o.y), z = fmaf(r.dt.z, tt, r.o.z);
-      sp = wave_in_box ? sample_pos(x, y, z, A) : sample_pos_clamped(x, y, z, A);
-      raw = cells[sp.idx];
-      empty = cell_empty(raw);
+      f = march_fetch(A, cells, r, s, wave_in_box);
+      empty = cell_empty(f.raw);
     }
     // every marching lane's sample in an empty cell: tau is exactly 0 for all of
     // them (no job, no alpha), so the round only counts and steps (bit-exact)
     const bool wave_empty = skip && __ballot(!empty) == 0;
     if (active) {
-      float4 sc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (!wave_empty) {
-        if (SH::kFB) quantise_weights<SH::kFB>(sp);   // filter_bits: volume and gradient weights
-        sc = classify<SH::kFB>(tfp, fn, trilerp_cell(raw, sp.ax, sp.ay, sp.az));
-      }
+      const float4 sc = wave_empty ? make_float4(0.f, 0.f, 0.f, 0.f) : march_classify<SH::kFB>(f, tfp, fn);
       cnt++;
-      if (sc.w > 0.0f && gate) {
-        const float a = 1.0f - cvr_expf(-(sc.w * h));
+      march_composite<PHONG>(r, f, sc, gate, grad, dst_a, s, active, [&](const ShadeJob& j) {
         if (EMIT) {
-          const f3 tx = vmad(r.dir, tt, r.tpos);        // tx_pos, box at [0, G]
-          q0 = make_float4(tx.x, tx.y, tx.z, a);
-          q1 = make_float4(sc.x, sc.y, sc.z, __int_as_float(slot));
-          if (PHONG) {
-            const f3 g = sample_gradient_cell(grad, sp);
-            q2 = make_float4(g.x, g.y, g.z, 0.0f);
-          }
+          job = j;
+          job.w = __int_as_float(slot);   // the fold takes 1 - dst.a from the alphas
         }
-        dst_a = fmaf(1.0f - dst_a, a, dst_a);
         pushed = true;
         any_job = true;
-        if (dst_a > 0.99f) active = false;
-      }
-      if (active) {
-        s = s + h;
-        active = s < r.D;
-      }
+      });
     }
     // the distance skip of an all-empty round (raymarch.hip march_ray, CS 3): when
     // every lane still marching sits in an empty cell at distance >= 2 from any
@@ -330,7 +433,7 @@ shaded_jobs_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
     // loads (the fewest any may: lanes stay at one sample index).  Skipped samples
     // make no job and no round, so the job list and its masks are unchanged.
     if (wave_empty && wave_in_box) {
-      const int q = active ? cell_skip_q(raw) : 0;
+      const int q = active ? cell_skip_q(f.raw) : 0;
       if (__ballot(active && q == 0) == 0 && __ballot(active) != 0 && active) {
         float dx = r.dt.x, dy = r.dt.y, dz = r.dt.z;
         asm volatile("" : "+v"(dx), "+v"(dy), "+v"(dz));
@@ -345,12 +448,7 @@ shaded_jobs_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
     const unsigned long long m = __ballot(pushed);
     if (m) {
       if (EMIT) {
-        if (pushed) {
-          float4* jp = J.jobs + (jbase + __popcll(m & lt)) * (PHONG ? 3 : 2);
-          jp[0] = q0;
-          jp[1] = q1;
-          if (PHONG) jp[2] = q2;
-        }
+        if (pushed) job.store<PHONG>(J.jobs + (jbase + __popcll(m & lt)) * ShadeJob::f4(PHONG));
         if (lane == 0) J.masks[rbase + rounds] = m;
         jbase += __popcll(m);
       }
@@ -364,12 +462,7 @@ shaded_jobs_kernel(typename SH::Args Q, const uint4* __restrict__ cells,
     J.tile_off[t] = tjobs;
     J.tile_roff[t] = rounds;
   }
-  if ((inside || A.packed) && samples) samples[oidx] = cnt;
-  if (tile_samples) {
-    const unsigned long long v = wave_sum(cnt);
-    if (lane == 0) tile_samples[t] = v;
-  }
-  if (shade_ctr && lane == 0) atomicAdd(&shade_ctr[0], (unsigned long long)tjobs);
+  store_march_counts(A, inside, oidx, t, lane, cnt, lane == 0 ? tjobs : 0u, samples, tile_samples, shade_ctr);
 }
 
 template <class SH, bool PHONG>
@@ -392,41 +485,35 @@ flat_shade_kernel(typename SH::Args Q, typename SH::Data data, FlatJobs J, int n
       // the cone traces; opacity, colour and gradient are read after them, and the
       // job index is rebuilt from the block (the shader's visibility / combine
       // halves: 32 B of spills per lane at the 96-VGPR budget instead of 72)
-      const float* jf = (const float*)(J.jobs + i * (PHONG ? 3 : 2));
-      const f3 tx{jf[0], jf[1], jf[2]};
-      const float4 cm = J.cam[__float_as_int(jf[7])];
+      constexpr int kTx = ShadeJob::kTx, kRgb = ShadeJob::kRgb, kG = ShadeJob::kG;
+      const float* jf = (const float*)(J.jobs + i * ShadeJob::f4(PHONG));
+      const f3 tx{jf[kTx], jf[kTx + 1], jf[kTx + 2]};
+      const float4 cm = J.cam[__float_as_int(jf[ShadeJob::kW])];
       const typename SH::Vis vis =
           SH::visibility(Q, data, tx, SH::world_pos(Q, tx), f3{cm.x, cm.y, cm.z}, nlit, nfetch);
       // (the lane from mbcnt, which the compiler does not equate with the thread
       // index: the first index and address are not kept live or spilled)
       const unsigned long long i2 =
           (unsigned long long)chunk * 64 + __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-      const float* jf2 = (const float*)(J.jobs + i2 * (PHONG ? 3 : 2));
+      const float* jf2 = (const float*)(J.jobs + i2 * ShadeJob::f4(PHONG));
       f3 g;
-      if (PHONG) g = f3{jf2[8], jf2[9], jf2[10]};
-      const f3 tx2{jf2[0], jf2[1], jf2[2]};
-      const f3 c = SH::combine(Q, vis, SH::world_pos(Q, tx2), f3{jf2[4], jf2[5], jf2[6]},
+      if (PHONG) g = f3{jf2[kG], jf2[kG + 1], jf2[kG + 2]};
+      const f3 tx2{jf2[kTx], jf2[kTx + 1], jf2[kTx + 2]};
+      const f3 c = SH::combine(Q, vis, SH::world_pos(Q, tx2), f3{jf2[kRgb], jf2[kRgb + 1], jf2[kRgb + 2]},
                                PHONG ? &g : nullptr);
-      const float a = jf2[3];
+      const float a = jf2[ShadeJob::kA];
       J.res[i2] = make_float4(c.x * a, c.y * a, c.z * a, a);
     }
   } else if (i < total) {
-    const float4* jp = J.jobs + i * (PHONG ? 3 : 2);
-    const float4 q0 = jp[0], q1 = jp[1];
-    const f3 tx{q0.x, q0.y, q0.z};
+    const float4* jp = J.jobs + i * ShadeJob::f4(PHONG);
+    ShadeJob j = ShadeJob::head(jp);
     const f3 hg{Q.a.half_grid[0], Q.a.half_grid[1], Q.a.half_grid[2]};
-    const f3 wp{tx.x - hg.x, tx.y - hg.y, tx.z - hg.z};
-    const float4 cm = J.cam[__float_as_int(q1.w)];
+    const f3 wp{j.tx.x - hg.x, j.tx.y - hg.y, j.tx.z - hg.z};
+    const float4 cm = J.cam[__float_as_int(j.w)];
     const f3 cam{cm.x, cm.y, cm.z};
-    const f3 rgb{q1.x, q1.y, q1.z};
-    f3 g;
-    if (PHONG) {
-      const float4 q2 = jp[2];
-      g = f3{q2.x, q2.y, q2.z};
-    }
-    const f3 c = SH::shade(Q, data, tx, wp, cam, rgb, PHONG ? &g : nullptr, nlit, nfetch);
-    const float a = q0.w;
-    J.res[i] = make_float4(c.x * a, c.y * a, c.z * a, a);
+    if (PHONG) j.g = ShadeJob::grad(jp);
+    const f3 c = SH::shade(Q, data, j.tx, wp, cam, j.rgb, PHONG ? &j.g : nullptr, nlit, nfetch);
+    J.res[i] = make_float4(c.x * j.a, c.y * j.a, c.z * j.a, j.a);
   }
   if (shade_ctr) {   // measurement only (secondary-fetch count of the roofline)
     const unsigned long long sl = wave_sum(nlit), sf = wave_sum(nfetch);
@@ -479,12 +566,10 @@ hipError_t launch_shaded_flat(const Ctx& c, const typename SH::Args& q, bool pho
       J.want_rounds = std::min(J.want_rounds, J.rcap);
     }
   }
-  if (phong)
-    hipLaunchKernelGGL((shaded_jobs_kernel<SH, true, false>), dim3(nt), dim3(64), lds, s, q, cells,
-                       grad, tf, J, samples, shade_ctr, tile_samples);
-  else
-    hipLaunchKernelGGL((shaded_jobs_kernel<SH, false, false>), dim3(nt), dim3(64), lds, s, q, cells,
-                       grad, tf, J, samples, shade_ctr, tile_samples);
+  with_phong(phong, [&](auto P) {
+    hipLaunchKernelGGL((shaded_jobs_kernel<SH, decltype(P)::value, false>), dim3(nt), dim3(64), lds, s, q,
+                       cells, grad, tf, J, samples, shade_ctr, tile_samples);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const unsigned long long kNoLimit = ~0ull;
   // (debug_flat_limit: a smaller capacity, to exercise the device-side fallback)
@@ -510,12 +595,10 @@ hipError_t launch_shaded_flat(const Ctx& c, const typename SH::Args& q, bool pho
       return launch_shaded_march<SH>(c, q, phong, data, out, samples, shade_ctr, tile_samples, s);
     }
   }
-  if (phong)
-    hipLaunchKernelGGL((shaded_jobs_kernel<SH, true, true>), dim3(nt), dim3(64), lds, s, q, cells,
-                       grad, tf, J, nullptr, nullptr, nullptr);
-  else
-    hipLaunchKernelGGL((shaded_jobs_kernel<SH, false, true>), dim3(nt), dim3(64), lds, s, q, cells,
-                       grad, tf, J, nullptr, nullptr, nullptr);
+  with_phong(phong, [&](auto P) {
+    hipLaunchKernelGGL((shaded_jobs_kernel<SH, decltype(P)::value, true>), dim3(nt), dim3(64), lds, s, q,
+                       cells, grad, tf, J, nullptr, nullptr, nullptr);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return e;
   // the shade grid covers the set's capacity; blocks past the frame's total exit
   const unsigned long long nch = ((unsigned long long)J.cap + 63) / 64;
@@ -523,12 +606,10 @@ hipError_t launch_shaded_flat(const Ctx& c, const typename SH::Args& q, bool pho
   const int nchunks = (int)nch, group = c.flat_group;
   const long long span = 8LL * group;                           // chunks per round of the XCDs
   const long long nb = (nchunks + span - 1) / span * span;      // every XCD gets whole groups
-  if (phong)
-    hipLaunchKernelGGL((flat_shade_kernel<SH, true>), dim3((unsigned)nb), dim3(64), 0, s, q, data, J,
-                       nchunks, group, shade_ctr);
-  else
-    hipLaunchKernelGGL((flat_shade_kernel<SH, false>), dim3((unsigned)nb), dim3(64), 0, s, q, data, J,
-                       nchunks, group, shade_ctr);
+  with_phong(phong, [&](auto P) {
+    hipLaunchKernelGGL((flat_shade_kernel<SH, decltype(P)::value>), dim3((unsigned)nb), dim3(64), 0, s, q,
+                       data, J, nchunks, group, shade_ctr);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return e;
   if ((e = launch_flat_fold(q.a, J, out, s)) != hipSuccess) return e;
   // the device-side fallback: renders the frame only if its list did not fit
@@ -554,14 +635,11 @@ hipError_t launch_shaded_march(const Ctx& c, const typename SH::Args& q, bool ph
   if (q.a.tf_n > kMaxTfLds) return hipErrorInvalidValue;
   const size_t lds = (size_t)(q.a.tf_n + 2) * sizeof(float4);
   const uint4* cells = (const uint4*)c.d_cells;   // sample_pos indexes from the first cell
-  if (phong)
-    hipLaunchKernelGGL((shaded_march_kernel<SH, true>), dim3(q.a.ntiles), dim3(64), lds, s, q,
+  with_phong(phong, [&](auto P) {
+    hipLaunchKernelGGL((shaded_march_kernel<SH, decltype(P)::value>), dim3(q.a.ntiles), dim3(64), lds, s, q,
                        cells, (const uint4*)c.d_grad, (const float4*)c.d_tf, data, out, samples,
                        shade_ctr, tile_samples, run_if);
-  else
-    hipLaunchKernelGGL((shaded_march_kernel<SH, false>), dim3(q.a.ntiles), dim3(64), lds, s, q,
-                       cells, (const uint4*)c.d_grad, (const float4*)c.d_tf, data, out, samples,
-                       shade_ctr, tile_samples, run_if);
+  });
   return hipGetLastError();
 }
 
