@@ -176,24 +176,15 @@ static cvr_status crtgt_advance(Ctx* c, const char* who, int max_samples, const 
   }
   if (unfinished) *unfinished = g.unfinished;
   if (!o) return CVR_OK;
-  const size_t npix = g.npix;
-  const int half = o->format == CVR_FORMAT_RGBA16F;
-  const size_t rgba_bytes = npix * (half ? 8 : 16), smp_bytes = npix * 4;
-  if (o->on_device) {
-    HIP_TRY(c, launch_crtgt_store(g.q, g.st, (float4*)o->rgba, (uint32_t*)o->samples,
-                                  (unsigned long long*)o->total, half, s));
-    return CVR_OK;
-  }
-  const cvr_status st = ensure_scratch(c, rgba_bytes + (o->samples ? smp_bytes : 0));
+  FrameOut fo;
+  const cvr_status st = bind_frame_output(c, o, g.npix, fo);
   if (st != CVR_OK) return st;
-  float4* d_out = (float4*)c->d_scratch;
-  uint32_t* d_smp = o->samples ? (uint32_t*)((char*)c->d_scratch + rgba_bytes) : nullptr;
-  HIP_TRY(c, launch_crtgt_store(g.q, g.st, d_out, d_smp, nullptr, half, s));
-  HIP_TRY(c, hipMemcpyAsync(o->rgba, d_out, rgba_bytes, hipMemcpyDeviceToHost, s));
-  if (o->samples) HIP_TRY(c, hipMemcpyAsync(o->samples, d_smp, smp_bytes, hipMemcpyDeviceToHost, s));
-  if (o->total) HIP_TRY(c, hipMemcpyAsync(o->total, g.st.ctr + 2, 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipStreamSynchronize(s));
-  return CVR_OK;
+  // the store adds the total up into a device output only: a host output's is
+  // read back from the rounds' own counter
+  if (!o->on_device) fo.d_total = nullptr;
+  HIP_TRY(c, launch_crtgt_store(g.q, g.st, fo.d_out, fo.d_samples, fo.d_total, fo.half, s));
+  if (!o->on_device) fo.d_total = g.st.ctr + 2;
+  return frame_output_finish(c, o, fo, s);
 }
 
 extern "C" {

@@ -270,7 +270,7 @@ cvr_status cvr_render_dosct(cvr_ctx* ctx, const cvr_frame* f, const cvr_dos_para
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t st) {
     return cvr::launch_dos(*c, Q, out, smp, shade, ts, st);
-  }, c->shade_flat != 0);
+  });
 }
 
 #pragma GCC visibility pop

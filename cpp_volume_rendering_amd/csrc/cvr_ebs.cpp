@@ -267,7 +267,7 @@ cvr_status cvr_render_extbsd(cvr_ctx* ctx, const cvr_frame* f, const cvr_ebs_par
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t st) {
     return cvr::launch_ebs(*c, Q, out, smp, shade, ts, st);
-  }, c->shade_flat != 0);
+  });
 }
 
 #pragma GCC visibility pop

@@ -160,76 +160,65 @@ float ebs_max_distance(const Ctx* c, const cvr_ebs_params* p);
 cvr_status ebs_prepare(Ctx* c, const char* who, const cvr_frame* f, const cvr_ebs_params* p,
                        const cvr_output* o, EbsArgs& Q, int& ntiles, size_t& npix);
 
-// Output handling shared by the shaded renderers (device or host buffers, the
-// sample total through per-tile counts + the sum epilogue, kernel timing events,
-// shade counters).  launch(out, samples, shade, tile_samples, stream).
+// One frame's output path, shared by every renderer: where the frame's kernels
+// write (the caller's device buffers, or the context's scratch for a host
+// output), the shared counters, the timing ring, and the read-back.  A frame
+// calls, in this order on its stream s: bind_frame_output, frame_counters_begin,
+// timed_launch, its own epilogue (launch_tile_epilogue when tile_samples is
+// set), frame_output_finish.  Defined in cvr_rc1pass.cpp.
+struct FrameOut {
+  float4* d_out = nullptr;
+  uint32_t* d_samples = nullptr;               // null: no per-pixel counts asked for
+  unsigned long long* d_total = nullptr;       // null: no sample total asked for
+  unsigned long long* tile_samples = nullptr;  // per-tile counts the sum epilogue adds into d_total
+  unsigned long long* shade = nullptr;         // option "shade_counters": the [3] counters, cleared
+  size_t rgba_bytes = 0, smp_bytes = 0;
+  int half = 0;                                // RGBA16F output
+  bool counters = false;                       // counters_acquire was called: release them
+};
+
+// Device outputs are bound as given; a host output renders into the context's
+// scratch (grown here), its total into the context's own counter.
+cvr_status bind_frame_output(Ctx* c, const cvr_output* o, size_t npix, FrameOut& fo);
+// With a total or shade counters in use: waits for the counters' last user on
+// another stream, clears a host output's total (a device total is the caller's:
+// the kernels add to it), and reserves tile_samples and the cleared shade counters.
+cvr_status frame_counters_begin(Ctx* c, const cvr_output* o, int ntiles, hipStream_t s, FrameOut& fo);
+// After the frame's epilogue: releases the counters; a host output is then
+// copied back and the stream drained.
+cvr_status frame_output_finish(Ctx* c, const cvr_output* o, const FrameOut& fo, hipStream_t s);
+
+// launch() between the events of option "kernel_timing" (cvr_read_kernel_times).
 template <class Launch>
-cvr_status render_shaded(Ctx* c, const cvr_output* o, int ntiles, size_t npix, const Launch& launch,
-                         bool flat_jobs = false) {
-  hipStream_t s = c->stream;
-  float4* d_out;
-  uint32_t* d_samples;
-  unsigned long long* d_total;
-  const size_t rgba_bytes = npix * (o->format == CVR_FORMAT_RGBA16F ? 8 : 16), smp_bytes = npix * 4;
-  if (o->on_device) {
-    d_out = (float4*)o->rgba;
-    d_samples = (uint32_t*)o->samples;
-    d_total = (unsigned long long*)o->total;
-  } else {
-    cvr_status st = ensure_scratch(c, rgba_bytes + (o->samples ? smp_bytes : 0));
-    if (st != CVR_OK) return st;
-    d_out = (float4*)c->d_scratch;
-    d_samples = o->samples ? (uint32_t*)((char*)c->d_scratch + rgba_bytes) : nullptr;
-    d_total = o->total ? c->d_total : nullptr;
-  }
-  // (flat shading keeps one job-list set per render stream: no wait for it here)
-  (void)flat_jobs;
-  const bool use_counters = d_total || c->shade_counters;
-  if (use_counters) {
-    cvr_status st = counters_acquire(c, s);
-    if (st != CVR_OK) return st;
-  }
-  if (d_total && !o->on_device) HIP_TRY(c, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
-  unsigned long long* tile_samples = nullptr;
-  if (d_total) {
-    if (c->tile_samples_n < ntiles) {
-      free_dev(c->d_tile_samples); c->tile_samples_n = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_tile_samples, (size_t)ntiles * 8));
-      HIP_TRY(c, hipMemsetAsync(c->d_tile_samples, 0, (size_t)ntiles * 8, s));
-      c->tile_samples_n = ntiles;
-    }
-    tile_samples = c->d_tile_samples;
-  }
-  unsigned long long* shade = nullptr;
-  if (c->shade_counters) {
-    if (!c->d_shade) HIP_TRY(c, hipMalloc((void**)&c->d_shade, 3 * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemsetAsync(c->d_shade, 0, 3 * sizeof(unsigned long long), s));
-    shade = c->d_shade;
-  }
+cvr_status timed_launch(Ctx* c, hipStream_t s, const Launch& launch) {
   const size_t nev = c->ev_start.size();
   const size_t slot = nev ? (size_t)(c->timed_frames % (long long)nev) : 0;
   if (nev) HIP_TRY(c, hipEventRecord(c->ev_start[slot], s));
-  HIP_TRY(c, launch(d_out, d_samples, shade, tile_samples, s));
+  HIP_TRY(c, launch());
   if (nev) {
     HIP_TRY(c, hipEventRecord(c->ev_stop[slot], s));
     c->timed_frames++;
   }
-  if (tile_samples) {
+  return CVR_OK;
+}
+
+// A shaded renderer's frame over that path: launch(out, samples, shade,
+// tile_samples, stream), then the sum epilogue of the sample total.
+template <class Launch>
+cvr_status render_shaded(Ctx* c, const cvr_output* o, int ntiles, size_t npix, const Launch& launch) {
+  hipStream_t s = c->stream;
+  FrameOut fo;
+  cvr_status st = bind_frame_output(c, o, npix, fo);
+  if (st == CVR_OK) st = frame_counters_begin(c, o, ntiles, s, fo);
+  if (st == CVR_OK)
+    st = timed_launch(c, s, [&] { return launch(fo.d_out, fo.d_samples, fo.shade, fo.tile_samples, s); });
+  if (st != CVR_OK) return st;
+  if (fo.tile_samples) {
     RenderPlan plan{};
     plan.ntiles = ntiles;
-    HIP_TRY(c, launch_tile_epilogue(nullptr, tile_samples, d_total, plan, nullptr, s));
+    HIP_TRY(c, launch_tile_epilogue(nullptr, fo.tile_samples, fo.d_total, plan, nullptr, s));
   }
-  if (use_counters) {
-    cvr_status st = counters_release(c, s);
-    if (st != CVR_OK) return st;
-  }
-  if (!o->on_device) {
-    HIP_TRY(c, hipMemcpyAsync(o->rgba, d_out, rgba_bytes, hipMemcpyDeviceToHost, s));
-    if (o->samples) HIP_TRY(c, hipMemcpyAsync(o->samples, d_samples, smp_bytes, hipMemcpyDeviceToHost, s));
-    if (o->total) HIP_TRY(c, hipMemcpyAsync(o->total, d_total, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-  }
-  return CVR_OK;
+  return frame_output_finish(c, o, fo, s);
 }
 
 }  // namespace cvr

@@ -223,7 +223,7 @@ static cvr_status preillum_march(Ctx* c, const char* who, const cvr_frame* f, co
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t st) {
     return cvr::launch_preillum(*c, Q, V, out, smp, shade, ts, st);
-  }, c->shade_flat != 0);
+  });
 }
 
 extern "C" {

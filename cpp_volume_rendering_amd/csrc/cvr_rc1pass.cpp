@@ -39,6 +39,65 @@ cvr_status ensure_scratch(Ctx* c, size_t bytes) {
   return CVR_OK;
 }
 
+cvr_status bind_frame_output(Ctx* c, const cvr_output* o, size_t npix, FrameOut& fo) {
+  fo.half = o->format == CVR_FORMAT_RGBA16F;
+  fo.rgba_bytes = npix * (fo.half ? 8 : 16);
+  fo.smp_bytes = npix * 4;
+  if (o->on_device) {
+    fo.d_out = (float4*)o->rgba;
+    fo.d_samples = (uint32_t*)o->samples;
+    fo.d_total = (unsigned long long*)o->total;
+    return CVR_OK;
+  }
+  const cvr_status st = ensure_scratch(c, fo.rgba_bytes + (o->samples ? fo.smp_bytes : 0));
+  if (st != CVR_OK) return st;
+  fo.d_out = (float4*)c->d_scratch;
+  fo.d_samples = o->samples ? (uint32_t*)((char*)c->d_scratch + fo.rgba_bytes) : nullptr;
+  fo.d_total = o->total ? c->d_total : nullptr;
+  return CVR_OK;
+}
+
+cvr_status frame_counters_begin(Ctx* c, const cvr_output* o, int ntiles, hipStream_t s, FrameOut& fo) {
+  fo.counters = fo.d_total || c->shade_counters;
+  if (fo.counters) {
+    const cvr_status st = counters_acquire(c, s);
+    if (st != CVR_OK) return st;
+  }
+  // device outputs: the kernel ADDS to *total (the caller zeroes it); host
+  // outputs: the context's own counter is reset here.
+  if (fo.d_total && !o->on_device) HIP_TRY(c, hipMemsetAsync(fo.d_total, 0, sizeof(unsigned long long), s));
+  // Sample total: every wave tile stores its count, a sum epilogue adds them up
+  // (one atomic per band; a per-wave atomic on one word serialises the frame).
+  if (fo.d_total) {
+    if (c->tile_samples_n < ntiles) {
+      free_dev(c->d_tile_samples); c->tile_samples_n = 0;
+      HIP_TRY(c, hipMalloc((void**)&c->d_tile_samples, (size_t)ntiles * 8));
+      HIP_TRY(c, hipMemsetAsync(c->d_tile_samples, 0, (size_t)ntiles * 8, s));
+      c->tile_samples_n = ntiles;
+    }
+    fo.tile_samples = c->d_tile_samples;
+  }
+  if (c->shade_counters) {   // measurement: shaded samples (gradient fetches), skipped samples
+    if (!c->d_shade) HIP_TRY(c, hipMalloc((void**)&c->d_shade, 3 * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemsetAsync(c->d_shade, 0, 3 * sizeof(unsigned long long), s));
+    fo.shade = c->d_shade;
+  }
+  return CVR_OK;
+}
+
+cvr_status frame_output_finish(Ctx* c, const cvr_output* o, const FrameOut& fo, hipStream_t s) {
+  if (fo.counters) {
+    const cvr_status st = counters_release(c, s);
+    if (st != CVR_OK) return st;
+  }
+  if (o->on_device) return CVR_OK;
+  HIP_TRY(c, hipMemcpyAsync(o->rgba, fo.d_out, fo.rgba_bytes, hipMemcpyDeviceToHost, s));
+  if (o->samples) HIP_TRY(c, hipMemcpyAsync(o->samples, fo.d_samples, fo.smp_bytes, hipMemcpyDeviceToHost, s));
+  if (o->total) HIP_TRY(c, hipMemcpyAsync(o->total, fo.d_total, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipStreamSynchronize(s));
+  return CVR_OK;
+}
+
 // The macro cells were built for one volume and one macro size.
 static void skip_drop_macro(Ctx::Skip& k) {
   free_dev(k.d_macro_minmax);
@@ -256,9 +315,9 @@ static bool view_close(const float a[7], const float b[7], int deg) {
   return std::fabs((double)a[6] - b[6]) <= rad * std::fabs((double)b[6]);
 }
 
-// nf frames (1..kMaxLaunchFrames) in one ray-march launch; nf = 1 is cvr_render_rc1pass.
-static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
-                                        const cvr_rc1pass_params* p, const cvr_output* outs) {
+// Every argument and state check of a launch of nf frames.
+static cvr_status check_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
+                                       const cvr_rc1pass_params* p, const cvr_output* outs) {
   const cvr_frame* f = frames;
   const cvr_output* o = outs;
   if (!f || !p || !o) return fail(c, CVR_ERR_ARG, "cvr_render_rc1pass: null argument");
@@ -284,24 +343,23 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
   }
   if (!c->d_cells) return fail(c, CVR_ERR_STATE, "cvr_render_rc1pass: no volume set");
   if (!c->d_tf) return fail(c, CVR_ERR_STATE, "cvr_render_rc1pass: no transfer function set");
-  const bool phong = p->apply_gradient_shading != 0;
-  if (phong && !c->d_grad)
+  if (p->apply_gradient_shading != 0 && !c->d_grad)
     return fail(c, CVR_ERR_STATE, "cvr_render_rc1pass: gradient shading needs cvr_set_gradient");
-  const bool packed = f->nranks > 1;
-  if (packed && (f->tile_size < 16 || f->tile_size % 16 != 0 || f->rank < 0 || f->rank >= f->nranks))
+  if (f->nranks > 1 && (f->tile_size < 16 || f->tile_size % 16 != 0 || f->rank < 0 || f->rank >= f->nranks))
     return fail(c, CVR_ERR_ARG, "cvr_render_rc1pass: bad tiling (tile %d, rank %d/%d)",
                 f->tile_size, f->rank, f->nranks);
+  return CVR_OK;
+}
 
-  cvr::Rc1passArgs A{};
-  cvr::RenderPlan plan{};
-  size_t npix;
-  fill_frame_args(c, f, p->step, A, plan.ntiles, npix);
+// Frame 0's kernel arguments but for the outputs and the launch order: the frame
+// constants, the shading, and the empty-space skip (per-cell flags, else the
+// macro cells' occupancy), which the state may have to build first.
+static cvr_status fill_rc1pass_args(Ctx* c, const cvr_frame* f, const cvr_rc1pass_params* p,
+                                    cvr::Rc1passArgs& A, int& ntiles, size_t& npix) {
+  fill_frame_args(c, f, p->step, A, ntiles, npix);
   set_phong_constants(A, p->ka, p->kd, p->ks, p->shininess, p->ispecular, p->light_pos);
   A.filter_bits = c->filter_bits;
-  A.tile_stats = nullptr;
   A.cost_time = c->cost_time;
-  A.occ = nullptr;
-  A.cell_skip = 0;
   {   // (the quad march ignores it)
     const cvr_status st = enable_cell_skip(c, A, c->cell_skip);
     if (st != CVR_OK) return st;
@@ -318,78 +376,48 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
     }
   }
   if (c->tile_stats) {
-    if (c->tile_stats_n < plan.ntiles) {
+    if (c->tile_stats_n < ntiles) {
       free_dev(c->d_tile_stats); c->tile_stats_n = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_tile_stats, (size_t)plan.ntiles * 32));
-      c->tile_stats_n = plan.ntiles;
+      HIP_TRY(c, hipMalloc((void**)&c->d_tile_stats, (size_t)ntiles * 32));
+      c->tile_stats_n = ntiles;
     }
     A.tile_stats = c->d_tile_stats;
   }
-  A.shade_ctr = nullptr;
-  const bool use_counters = c->shade_counters || o->total;
-  if (use_counters) {
-    cvr_status st = counters_acquire(c, c->stream);
-    if (st != CVR_OK) return st;
-  }
-  if (c->shade_counters) {   // measurement: shaded samples (gradient fetches), skipped samples
-    if (!c->d_shade) HIP_TRY(c, hipMalloc((void**)&c->d_shade, 3 * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMemsetAsync(c->d_shade, 0, 3 * sizeof(unsigned long long), c->stream));
-    A.shade_ctr = c->d_shade;
-  }
+  return CVR_OK;
+}
+
+// How the frame's ntiles wave tiles are cut into work (options only).
+static cvr::RenderPlan make_render_plan(const Ctx* c, int ntiles) {
+  cvr::RenderPlan plan{};
+  plan.ntiles = ntiles;
   plan.quad_pct = c->filter_bits ? 0 : c->quad_pct;   // the quad march has no filter_bits variant
-  {
-    // Bands are cut by predicted work, so one may hold more than 1/8 of the
-    // tiles: up to band_cap % of the even share (default 130;
-    // tile_epilogue_kernel moves the band boundaries the least that fits the
-    // cap); every band gets that many slots (+3 per quad-split tile), and the
-    // slots past a band's entries are empty workgroups.
-    const int seg_avg = (plan.ntiles + 7) / 8;
-    const int cap = (int)(((long long)seg_avg * c->band_cap_pct + 99) / 100);
-    plan.max_seg = std::min(std::min(plan.ntiles, cap), cvr::kMaxBandTiles);
-    if (plan.max_seg < seg_avg) plan.max_seg = seg_avg;   // (too large to order; see can_order)
-    int per_band = plan.max_seg + 3 * (int)(((long long)plan.max_seg * plan.quad_pct) / 100);
-    per_band = (per_band + 3) & ~3;   // whole groups of 4 waves per workgroup (raymarch.hip)
-    plan.order_slots = 8 * per_band;
-    plan.boost = (int)(((long long)seg_avg * c->boost_pct) / 100);
-    plan.keep = c->debug_keep;
-    plan.epi_stop = c->epi_stop;
-  }
+  // Bands are cut by predicted work, so one may hold more than 1/8 of the
+  // tiles: up to band_cap % of the even share (default 130;
+  // tile_epilogue_kernel moves the band boundaries the least that fits the
+  // cap); every band gets that many slots (+3 per quad-split tile), and the
+  // slots past a band's entries are empty workgroups.
+  const int seg_avg = (ntiles + 7) / 8;
+  const int cap = (int)(((long long)seg_avg * c->band_cap_pct + 99) / 100);
+  plan.max_seg = std::min(std::min(ntiles, cap), cvr::kMaxBandTiles);
+  if (plan.max_seg < seg_avg) plan.max_seg = seg_avg;   // (too large to order; see render_rc1pass_frames)
+  int per_band = plan.max_seg + 3 * (int)(((long long)plan.max_seg * plan.quad_pct) / 100);
+  per_band = (per_band + 3) & ~3;   // whole groups of 4 waves per workgroup (raymarch.hip)
+  plan.order_slots = 8 * per_band;
+  plan.boost = (int)(((long long)seg_avg * c->boost_pct) / 100);
+  plan.keep = c->debug_keep;
+  plan.epi_stop = c->epi_stop;
+  return plan;
+}
 
-  HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  float4* d_out;
-  uint32_t* d_samples;
-  unsigned long long* d_total;
-  A.out_half = o->format == CVR_FORMAT_RGBA16F;
-  size_t rgba_bytes = npix * (A.out_half ? 8 : 16), smp_bytes = npix * 4;
-  if (o->on_device) {
-    d_out = (float4*)o->rgba;
-    d_samples = (uint32_t*)o->samples;
-    d_total = (unsigned long long*)o->total;
-  } else {
-    cvr_status st = ensure_scratch(c, rgba_bytes + (o->samples ? smp_bytes : 0));
-    if (st != CVR_OK) return st;
-    d_out = (float4*)c->d_scratch;
-    d_samples = o->samples ? (uint32_t*)((char*)c->d_scratch + rgba_bytes) : nullptr;
-    d_total = o->total ? c->d_total : nullptr;
-  }
-  // device outputs: the kernel ADDS to *total (the caller zeroes it); host
-  // outputs: the context's own counter is reset here.
-  if (d_total && !o->on_device) HIP_TRY(c, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), s));
-
-  // Longest-first (LPT) order learned three frames back (same plan): the kernel
-  // records each wave tile's critical path into this frame's slot, and the
-  // slot's order is rebuilt from it on the side stream while the next frame
-  // renders (tile_epilogue_kernel: work-balanced XCD bands + bucket LPT).
-  const bool can_order = c->use_order == 1 && (plan.ntiles + 7) / 8 <= cvr::kMaxBandTiles;
-  A.interleave = c->use_order == 2;
-  float vsig[7];
-  view_signature(A, vsig);
-  // frames 1.. of a multi-frame launch: their views (the rest of A is frame 0's)
-  cvr::LaunchFrames lf;
+// The views and outputs of a launch's frames (frames 1.. differ from frame 0,
+// whose arguments are A, in nothing else).  Returns whether every frame is near
+// frame 0's view vsig: one launch order serves them all.
+static bool fill_launch_views(Ctx* c, const cvr_frame* frames, int nf, const cvr_rc1pass_params* p,
+                              const cvr_output* outs, const cvr::Rc1passArgs& A, const float vsig[7],
+                              cvr::LaunchFrames& lf) {
   lf.n = nf;
   lf.grid = 0;
-  bool views_close = true;   // every frame of the launch near frame 0's view (one launch order)
+  bool views_close = true;
   for (int i = 0; i < nf; i++) {
     cvr::Rc1passArgs Ai = A;
     if (i > 0) {
@@ -412,14 +440,18 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
     lf.out[i] = (float4*)outs[i].rgba;
     lf.samples[i] = (uint32_t*)outs[i].samples;
   }
-  if (nf > 1) plan.frames = &lf;
-  const int key = (plan.ntiles << 2) ^ (plan.quad_pct << 24) ^
-                  (packed ? (f->rank << 8) ^ (f->nranks << 12) ^ 1 : 0);
-  const int* order = nullptr;
-  uint32_t* tile_cost = nullptr;
-  // One slot per render stream: frames issued on different streams may overlap
-  // on the device (the screen-tile split alternates two), and a slot's order,
-  // costs and rebuilds stay in its stream's order.  async_order: slots rotate.
+  return views_close;
+}
+
+// The launch order (Ctx::OrderSlot).  Longest-first (LPT) order learned on an
+// earlier frame of the same plan: the kernel records each wave tile's critical
+// path into the slot's costs, and the slot's order is rebuilt from them
+// (tile_epilogue_kernel: work-balanced XCD bands + bucket LPT).
+//
+// One slot per render stream: frames issued on different streams may overlap
+// on the device (the screen-tile split alternates two), and a slot's order,
+// costs and rebuilds stay in its stream's order.  async_order: slots rotate.
+static cvr_status order_slot_for_stream(Ctx* c, hipStream_t s, Ctx::OrderSlot*& os) {
   int si = -1;
   if (c->async_order) {
     si = (int)(c->frame_no % 3);
@@ -436,83 +468,84 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
       o.frames = 0;
     }
   }
-  Ctx::OrderSlot& os = c->oslot[si];
-  if (can_order) {
-    if (c->async_order && !c->side) {   // side stream + events only for side-stream sorts
-      int lo = 0, hi = 0;
-      HIP_TRY(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
-      HIP_TRY(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, hi));
-      HIP_TRY(c, hipEventCreateWithFlags(&c->ev_frame, hipEventDisableTiming));
-      for (auto& o : c->oslot) HIP_TRY(c, hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
-    }
-    // the slot's previous sort must be done before this frame reads its order
-    // and overwrites its costs (it ran alongside the previous frame)
-    if (os.pending) HIP_TRY(c, hipStreamWaitEvent(s, os.done, 0));
-    if (os.units < plan.order_slots || os.ntiles < plan.ntiles) {
-      if (c->side) HIP_TRY(c, hipStreamSynchronize(c->side));
-      free_dev(os.d_order);
-      free_dev(os.d_cost);
-      os.units = os.ntiles = 0;
-      os.valid = 0;
-      HIP_TRY(c, hipMalloc((void**)&os.d_order, (size_t)plan.order_slots * sizeof(int)));
-      HIP_TRY(c, hipMalloc((void**)&os.d_cost, (size_t)plan.ntiles * sizeof(uint32_t) + 64));
-      HIP_TRY(c, hipMemsetAsync(os.d_cost, 0, (size_t)plan.ntiles * sizeof(uint32_t) + 64, s));
-      os.units = plan.order_slots;
-      os.ntiles = plan.ntiles;
-    }
-    order = (os.valid && os.key == key) ? os.d_order : nullptr;
-    // an order learned on a distant view costs more than none (interleaved
-    // screen order): measured +18 % mean over the 24 reference views
-    if (order && os.has_view && !view_close(vsig, os.view, c->stale_deg)) order = nullptr;
-    if (!views_close) order = nullptr;   // frames far apart in one launch: no shared order
-    tile_cost = os.d_cost;
+  os = &c->oslot[si];
+  return CVR_OK;
+}
+
+// The slot's order and cost buffers for this plan; under async_order also the
+// side stream and its events, and the wait for the slot's sort in flight.
+static cvr_status order_slot_reserve(Ctx* c, Ctx::OrderSlot& os, const cvr::RenderPlan& plan, hipStream_t s) {
+  if (c->async_order && !c->side) {   // side stream + events only for side-stream sorts
+    int lo = 0, hi = 0;
+    HIP_TRY(c, hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIP_TRY(c, hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, hi));
+    HIP_TRY(c, hipEventCreateWithFlags(&c->ev_frame, hipEventDisableTiming));
+    for (auto& o : c->oslot) HIP_TRY(c, hipEventCreateWithFlags(&o.done, hipEventDisableTiming));
   }
-  // without an order, tiles go to the XCDs interleaved (tile t on XCD t mod 8):
-  // it balances any view, where contiguous bands need the learned costs
-  if (!order && c->use_order == 1) A.interleave = 1;
-  // Sample total: every wave tile stores its count, a sum epilogue adds them up
-  // (one atomic per band; a per-wave atomic on one word serialises the frame).
-  unsigned long long* tile_samples = nullptr;
-  if (d_total) {
-    if (c->tile_samples_n < plan.ntiles) {
-      free_dev(c->d_tile_samples); c->tile_samples_n = 0;
-      HIP_TRY(c, hipMalloc((void**)&c->d_tile_samples, (size_t)plan.ntiles * 8));
-      HIP_TRY(c, hipMemsetAsync(c->d_tile_samples, 0, (size_t)plan.ntiles * 8, s));
-      c->tile_samples_n = plan.ntiles;
-    }
-    tile_samples = c->d_tile_samples;
-  }
-  const size_t nev = c->ev_start.size();
-  const size_t slot = nev ? (size_t)(c->timed_frames % (long long)nev) : 0;
-  if (nev) HIP_TRY(c, hipEventRecord(c->ev_start[slot], s));
-  HIP_TRY(c, cvr::launch_rc1pass(*c, A, phong, d_out, d_samples, tile_samples, order, tile_cost,
-                                 plan, s));
-  if (nev) {
-    HIP_TRY(c, hipEventRecord(c->ev_stop[slot], s));
-    c->timed_frames++;
-  }
-  // The order is rebuilt every order_interval-th frame (and whenever it is
-  // missing or stale for this plan): costs shift slowly between frames, and
-  // the rebuild (~15 us on the frame's stream) would otherwise cost ~10 %.
-  // ... and only while the camera holds still (or moves little) from frame to
-  // frame: when every frame jumps to a distant view, a new order would never be
-  // used and its rebuild (~15 us on the frame's stream) is skipped
+  // the slot's previous sort must be done before this frame reads its order
+  // and overwrites its costs (it ran alongside the previous frame)
+  if (os.pending) HIP_TRY(c, hipStreamWaitEvent(s, os.done, 0));
+  if (os.units >= plan.order_slots && os.ntiles >= plan.ntiles) return CVR_OK;
+  if (c->side) HIP_TRY(c, hipStreamSynchronize(c->side));
+  free_dev(os.d_order);
+  free_dev(os.d_cost);
+  os.units = os.ntiles = 0;
+  os.valid = 0;
+  HIP_TRY(c, hipMalloc((void**)&os.d_order, (size_t)plan.order_slots * sizeof(int)));
+  HIP_TRY(c, hipMalloc((void**)&os.d_cost, (size_t)plan.ntiles * sizeof(uint32_t) + 64));
+  HIP_TRY(c, hipMemsetAsync(os.d_cost, 0, (size_t)plan.ntiles * sizeof(uint32_t) + 64, s));
+  os.units = plan.order_slots;
+  os.ntiles = plan.ntiles;
+  return CVR_OK;
+}
+
+// The order this frame launches under, or null: the slot's, if it was built for
+// this plan (key) on a view near this one.
+static const int* order_for_frame(const Ctx* c, const Ctx::OrderSlot& os, int key, const float vsig[7],
+                                  bool views_close) {
+  if (!os.valid || os.key != key) return nullptr;
+  // an order learned on a distant view costs more than none (interleaved
+  // screen order): measured +18 % mean over the 24 reference views
+  if (os.has_view && !view_close(vsig, os.view, c->stale_deg)) return nullptr;
+  return views_close ? os.d_order : nullptr;   // frames far apart in one launch: no shared order
+}
+
+// The slot's order is (being) built from this frame's costs.
+static void order_commit(Ctx::OrderSlot& os, int key, const float vsig[7]) {
+  os.valid = 1;
+  os.key = key;
+  std::memcpy(os.view, vsig, sizeof(os.view));
+  os.has_view = true;
+}
+
+// Whether this frame's epilogue rebuilds the order; counts the frame on the slot.
+// The order is rebuilt every order_interval-th frame (and whenever it is
+// missing or stale for this plan): costs shift slowly between frames, and
+// the rebuild (~15 us on the frame's stream) would otherwise cost ~10 %.
+// ... and only while the camera holds still (or moves little) from frame to
+// frame: when every frame jumps to a distant view, a new order would never be
+// used and its rebuild (~15 us on the frame's stream) is skipped
+static bool order_rebuild_due(const Ctx* c, Ctx::OrderSlot& os, const float vsig[7], bool views_close,
+                              bool have_order) {
   const bool steady = views_close && (!os.has_last || view_close(vsig, os.last_view, c->stale_deg));
-  std::memcpy(os.last_view, vsig, sizeof(vsig));
+  std::memcpy(os.last_view, vsig, sizeof(os.last_view));
   os.has_last = true;
-  const bool rebuild = tile_cost && !c->async_order && steady &&
-                       (!order || os.frames % std::max(1, c->order_interval) == 0);
+  const bool due = !have_order || os.frames % std::max(1, c->order_interval) == 0;
   os.frames++;
+  return !c->async_order && steady && due;
+}
+
+// After the march: the sample total's sum and the order for a later frame, in
+// one epilogue on the frame's stream, or (async_order) the order on the side stream.
+static cvr_status launch_rc1pass_epilogue(Ctx* c, Ctx::OrderSlot& os, const cvr::RenderPlan& plan, int key,
+                                          const float vsig[7], bool rebuild, uint32_t* tile_cost,
+                                          const FrameOut& fo, hipStream_t s) {
   if (rebuild) {
-    // one epilogue on the frame's stream: sum + order for the next frame
-    HIP_TRY(c, cvr::launch_tile_epilogue(tile_cost, tile_samples, d_total, plan, os.d_order, s));
+    HIP_TRY(c, cvr::launch_tile_epilogue(tile_cost, fo.tile_samples, fo.d_total, plan, os.d_order, s));
     os.pending = false;
-    os.valid = 1;
-    os.key = key;
-    std::memcpy(os.view, vsig, sizeof(vsig));
-    os.has_view = true;
-  } else if (tile_samples) {
-    HIP_TRY(c, cvr::launch_tile_epilogue(nullptr, tile_samples, d_total, plan, nullptr, s));
+    order_commit(os, key, vsig);
+  } else if (fo.tile_samples) {
+    HIP_TRY(c, cvr::launch_tile_epilogue(nullptr, fo.tile_samples, fo.d_total, plan, nullptr, s));
   }
   if (tile_cost && c->async_order) {
     HIP_TRY(c, hipEventRecord(c->ev_frame, s));
@@ -520,23 +553,66 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
     HIP_TRY(c, cvr::launch_tile_epilogue(tile_cost, nullptr, nullptr, plan, os.d_order, c->side));
     HIP_TRY(c, hipEventRecord(os.done, c->side));
     os.pending = true;
-    os.valid = 1;
-    os.key = key;
-    std::memcpy(os.view, vsig, sizeof(vsig));
-    os.has_view = true;
-  }
-  c->frame_no++;
-  if (use_counters) {
-    cvr_status st = counters_release(c, s);
-    if (st != CVR_OK) return st;
-  }
-  if (!o->on_device) {
-    HIP_TRY(c, hipMemcpyAsync(o->rgba, d_out, rgba_bytes, hipMemcpyDeviceToHost, s));
-    if (o->samples) HIP_TRY(c, hipMemcpyAsync(o->samples, d_samples, smp_bytes, hipMemcpyDeviceToHost, s));
-    if (o->total) HIP_TRY(c, hipMemcpyAsync(o->total, d_total, 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
+    order_commit(os, key, vsig);
   }
   return CVR_OK;
+}
+
+// nf frames (1..kMaxLaunchFrames) in one ray-march launch; nf = 1 is cvr_render_rc1pass.
+static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
+                                        const cvr_rc1pass_params* p, const cvr_output* outs) {
+  cvr_status st = check_rc1pass_frames(c, frames, nf, p, outs);
+  if (st != CVR_OK) return st;
+  const cvr_frame* f = frames;
+  const cvr_output* o = outs;
+  cvr::Rc1passArgs A{};
+  int ntiles;
+  size_t npix;
+  st = fill_rc1pass_args(c, f, p, A, ntiles, npix);
+  if (st != CVR_OK) return st;
+  cvr::RenderPlan plan = make_render_plan(c, ntiles);
+
+  HIP_TRY(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  FrameOut fo;
+  st = bind_frame_output(c, o, npix, fo);
+  if (st == CVR_OK) st = frame_counters_begin(c, o, ntiles, s, fo);
+  if (st != CVR_OK) return st;
+  A.out_half = fo.half;
+  A.shade_ctr = fo.shade;
+
+  float vsig[7];
+  view_signature(A, vsig);
+  cvr::LaunchFrames lf;
+  const bool views_close = fill_launch_views(c, frames, nf, p, outs, A, vsig, lf);
+  if (nf > 1) plan.frames = &lf;
+  const int key = (ntiles << 2) ^ (plan.quad_pct << 24) ^
+                  (f->nranks > 1 ? (f->rank << 8) ^ (f->nranks << 12) ^ 1 : 0);
+  Ctx::OrderSlot* os;
+  st = order_slot_for_stream(c, s, os);
+  if (st != CVR_OK) return st;
+  const int* order = nullptr;
+  uint32_t* tile_cost = nullptr;
+  if (c->use_order == 1 && (ntiles + 7) / 8 <= cvr::kMaxBandTiles) {   // else too large to order
+    st = order_slot_reserve(c, *os, plan, s);
+    if (st != CVR_OK) return st;
+    order = order_for_frame(c, *os, key, vsig, views_close);
+    tile_cost = os->d_cost;
+  }
+  // without an order, tiles go to the XCDs interleaved (tile t on XCD t mod 8):
+  // it balances any view, where contiguous bands need the learned costs
+  A.interleave = c->use_order == 2 || (!order && c->use_order == 1);
+
+  const bool phong = p->apply_gradient_shading != 0;
+  st = timed_launch(c, s, [&] {
+    return cvr::launch_rc1pass(*c, A, phong, fo.d_out, fo.d_samples, fo.tile_samples, order, tile_cost, plan, s);
+  });
+  if (st != CVR_OK) return st;
+  const bool rebuild = order_rebuild_due(c, *os, vsig, views_close, order != nullptr) && tile_cost;
+  st = launch_rc1pass_epilogue(c, *os, plan, key, vsig, rebuild, tile_cost, fo, s);
+  if (st != CVR_OK) return st;
+  c->frame_no++;
+  return frame_output_finish(c, o, fo, s);
 }
 
 extern "C" {

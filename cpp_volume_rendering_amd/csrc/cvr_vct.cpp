@@ -321,7 +321,7 @@ cvr_status cvr_render_vct(cvr_ctx* ctx, const cvr_frame* f, const cvr_vct_params
   return render_shaded(c, o, ntiles, npix, [&](float4* out, uint32_t* smp, unsigned long long* shade,
                                                 unsigned long long* ts, hipStream_t s) {
     return cvr::launch_vct(*c, Q, data, out, smp, shade, ts, s);
-  }, c->shade_flat != 0);
+  });
 }
 
 #pragma GCC visibility pop
