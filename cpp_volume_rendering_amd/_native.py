@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "cvr_render_crtgt",
     "cvr_vct_params_default", "cvr_tf1d_opacity_lut", "cvr_vct_set_opacity", "cvr_vct_precompute",
     "cvr_vct_info", "cvr_vct_read_pyramid", "cvr_vct_read_table", "cvr_render_vct",
+    "cvr_sbtm_params_default", "cvr_render_sbtm", "cvr_sbtm_read_occlusion",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
     "cvr_decode_tiles", "cvr_comm_init_local", "cvr_create_group", "cvr_group_size",
@@ -159,6 +160,12 @@ class VctParams(ctypes.Structure):
                 ("cone_initial_step", ctypes.c_float), ("cone_apex_angle_deg", ctypes.c_float),
                 ("apply_correction", ctypes.c_int), ("correction_factor", ctypes.c_float),
                 ("samples", ctypes.c_int)]
+
+
+class SbtmParams(ctypes.Structure):
+    _fields_ = [("step", ctypes.c_float), ("cone_half_angle_deg", ctypes.c_float),
+                ("grid_x", ctypes.c_int), ("grid_y", ctypes.c_int), ("attenuation", ctypes.c_float),
+                ("max_passes", ctypes.c_int), ("z_near", ctypes.c_float), ("z_far", ctypes.c_float)]
 
 
 class VctPyramidInfo(ctypes.Structure):
@@ -290,6 +297,10 @@ def lib() -> ctypes.CDLL:
         "cvr_vct_read_table": ([P, FP], I),
         "cvr_render_vct": ([P, ctypes.POINTER(Frame), ctypes.POINTER(VctParams),
                             ctypes.POINTER(Output)], I),
+        "cvr_sbtm_params_default": ([ctypes.POINTER(SbtmParams)], None),
+        "cvr_render_sbtm": ([P, ctypes.POINTER(Frame), ctypes.POINTER(SbtmParams),
+                             ctypes.POINTER(Output)], I),
+        "cvr_sbtm_read_occlusion": ([P, I, I, FP], I),
         "cvr_iso_params_default": ([I, ctypes.POINTER(IsoParams)], None),
         "cvr_render_iso": ([P, ctypes.POINTER(Frame), ctypes.POINTER(IsoParams),
                             ctypes.POINTER(Output)], I),

@@ -102,6 +102,7 @@ static void derived_drop(Ctx* c, Changed what) {
   light_cache_drop(c, destroy);
   if (destroy) crtgt_release(c); else crtgt_invalidate(c);
   vct_drop(c, volume_gone);
+  sbtm_drop(c);
   if (volume_gone) iso_drop(c);
 }
 
@@ -360,7 +361,7 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
     return b;
   }
   return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
-         c->lc.bytes + c->gt.bytes + c->vct.bytes;
+         c->lc.bytes + c->gt.bytes + c->vct.bytes + c->sbtm.bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {

@@ -1,6 +1,6 @@
 // cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
 // cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_crtgt.cpp,
-// cvr_vct.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
+// cvr_vct.cpp, cvr_sbtm.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
 // the host arithmetic, and the frame set-up common to the renderers.  Host only:
 // never included by a .hip file or a kernel header.
 //
@@ -150,6 +150,10 @@ void crtgt_release(Ctx* c);
 // cvr_vct.cpp: a new volume drops the pyramid and the table, a new TF the table
 // and the opacities; the context's end frees everything
 void vct_drop(Ctx* c, bool pyramid);
+
+// cvr_sbtm.cpp: the eye buffer and the occlusion planes hold nothing between frames;
+// a new volume or TF and the context's end free them
+void sbtm_drop(Ctx* c);
 
 // cvr_dos.cpp, cvr_ebs.cpp: a frame's kernel arguments (also for the light cache)
 void resolve_cone_params(const Ctx* c, const cvr_dos_params* p, cvr_cone_params cp[2]);

@@ -241,6 +241,44 @@ struct VctData {
   const VctStep* steps;              // [samples]
 };
 
+// Slice-based directional occlusion (sbtm.hip).  One slice as its pass reads it:
+// everything here is the host's float arithmetic (cvr_sbtm.cpp, DESIGN.md 5d''').
+constexpr int kSbtmMaxBatch = 16;        // slices one launch advances (option sbtm_slices_per_launch)
+constexpr int kSbtmTile = 64;            // the blocked form's screen tile, pixels a side
+constexpr int kSbtmHalo = 16;            // most halo pixels per side its LDS region holds
+constexpr int kSbtmRegion = kSbtmTile + 2 * kSbtmHalo;
+constexpr int kSbtmThreads = 512;
+struct SbtmSlice {
+  float depth;                       // view depth of the slice's quad
+  float c[3];                        // the quad's centre
+  float cvx, cvy;                    // CVector (equation 12)
+  int rx, ry;                        // tap radius in pixels (the proven bound)
+  int plane;                         // the occlusion plane this slice writes (it reads the other)
+};
+struct SbtmBatch {
+  int n;                             // slices of this launch
+  int ex, ey;                        // the summed radii: the halo loaded around the tile
+  SbtmSlice s[kSbtmMaxBatch];
+};
+struct SbtmArgs {
+  Rc1passArgs a;                     // ray generation, volume, TF size, filter_bits
+  float right[3], up[3];             // cam_right, cam_up
+  float half_diag;                   // volume_diagonal / 2 (voxels, unscaled)
+  float att;                         // UITransparencyScale
+  int gx, gy;
+  float gxy;                         // GridSize.x * GridSize.y
+  float tapx[CVR_SBTM_MAX_GRID];     // the grid's p.x per xpos_sample, p.y per ypos_sample
+  float tapy[CVR_SBTM_MAX_GRID];
+};
+struct SbtmPlanes {
+  uint2* eye;                        // RGBA16F
+  uint16_t* occ;                     // two R16F planes, plane p at occ + p * W * H
+  uint16_t* occ_out;                 // the blocked form stores its tiles' planes here, never into occ:
+                                     // another workgroup of the launch may still load its halo from occ
+  uint32_t* samples;                 // per-pixel fragments kept, or null
+  unsigned long long* total;         // their sum is added here, or null
+};
+
 // Isosurface ray-casters with block skipping (iso.hip): the shaders' uniforms.
 struct IsoArgs {
   Rc1passArgs a;                     // ray, volume, Blinn-Phong constants, tiles
@@ -538,6 +576,19 @@ struct Ctx {
     int steps_valid = 0;
     size_t bytes = 0;                  // all of the above (cvr_device_bytes)
   } vct;
+  // slice-based directional occlusion (cvr_sbtm.cpp): the eye buffer and two sets of
+  // the two occlusion planes of the last frame's viewport (16 B per pixel; set `cur`
+  // holds the planes, a blocked launch reads it and writes the other), and what the
+  // read-only options sbtm_slices / sbtm_launches report
+  struct Sbtm {
+    uint2* d_eye = nullptr;
+    uint16_t* d_occ = nullptr;         // set k at d_occ + k * 2 * npix
+    int cur = 0;
+    size_t npix = 0;
+    size_t bytes = 0;                  // all of the above (cvr_device_bytes)
+    int slices = 0, launches = 0;
+  } sbtm;
+  int sbtm_slices_per_launch = 1;    // option "sbtm_slices_per_launch" (default: by measurement, DESIGN.md 5d''')
   unsigned long long* d_tile_samples = nullptr;   // per-wave-tile sample counts (zeroed)
   int tile_samples_n = 0;
   // d_tile_samples and d_shade are one set per context: a frame that uses them on
@@ -646,6 +697,15 @@ hipError_t launch_vct_schedule(const VctLevel* d_levels, int nl, float initial, 
                                hipStream_t s);
 hipError_t launch_vct(const Ctx& c, const VctArgs& q, const VctData& data, float4* out, uint32_t* samples,
                       unsigned long long* shade, unsigned long long* tile_samples, hipStream_t s);
+// sbtm.hip: the frame's clear (eye 0, both occlusion planes 1, counts 0), one launch
+// of b.n consecutive slices (b.n == 1: the plain form, occlusion read from global
+// memory, in place; else the blocked form, b.ex / b.ey <= kSbtmHalo, which reads
+// p.occ and leaves the planes in p.occ_out), and the eye buffer's copy into an
+// output image
+hipError_t launch_sbtm_clear(const SbtmPlanes& p, int W, int H, hipStream_t s);
+hipError_t launch_sbtm_slices(const Ctx& c, const SbtmArgs& q, const SbtmBatch& b, const SbtmPlanes& p,
+                              hipStream_t s);
+hipError_t launch_sbtm_store(const SbtmPlanes& p, int W, int H, float4* out, int half, hipStream_t s);
 // iso.hip: raw per-block extremes (uint2), and the isosurface march (variant 0/1)
 hipError_t launch_block_minmax(const void* vox, int bpv, const int N[3], const int nb[3], uint2* out,
                                hipStream_t s);

@@ -132,6 +132,8 @@ const Option kOptions[] = {
        if (value != c->band_cap_pct) invalidate_orders(c);   // the learned orders are laid out for the old cap
        return CVR_OK;
      }},
+    // slices one launch of the slice-based renderer advances (sbtm.hip's blocked form; 1: plain)
+    {"sbtm_slices_per_launch", &Ctx::sbtm_slices_per_launch, nullptr, 1, kSbtmMaxBatch, nullptr, nullptr, nullptr},
     // read-only
     {"cell_flags_active", nullptr, [](const Ctx* c) { return (int)(c->skip.flags_valid && !c->skip.flags_oom); },
      1, 0, nullptr, nullptr, nullptr},
@@ -151,6 +153,9 @@ const Option kOptions[] = {
      1, 0, nullptr, nullptr, nullptr},
     {"light_cache_builds", nullptr, [](const Ctx* c) { return c->lc.builds; }, 1, 0, nullptr, nullptr, nullptr},
     {"vct_pyramid_builds", nullptr, [](const Ctx* c) { return c->vct.builds; }, 1, 0, nullptr, nullptr, nullptr},
+    // the last slice-based frame: slices drawn, and the launches that drew them
+    {"sbtm_slices", nullptr, [](const Ctx* c) { return c->sbtm.slices; }, 1, 0, nullptr, nullptr, nullptr},
+    {"sbtm_launches", nullptr, [](const Ctx* c) { return c->sbtm.launches; }, 1, 0, nullptr, nullptr, nullptr},
 };
 
 const Option* find_option(const char* key) {

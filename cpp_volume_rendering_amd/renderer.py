@@ -931,6 +931,46 @@ class RC1PVoxelConeTracingSGPU(RayCasting1Pass):
     _ENTRY = "cvr_render_vct"
 
 
+class SBTMDirectionalOcclusionShading(RayCasting1Pass):
+    """HIP implementation of SBTMDirectionalOcclusionShading
+    (cppvolrend/structured/sbtmdos/sbtmdosrenderer.cpp): Schott et al.'s slice-based
+    directional occlusion, view-aligned slices composited front to back through an eye buffer
+    and two occlusion buffers.  A BaseVolumeRenderer through RayCasting1Pass, whose Init,
+    Redraw and multiscaling it shares; there is no light and no gradient.  A frame is whole:
+    no screen tiles, no device groups."""
+
+    def __init__(self, device: int = 0):
+        super().__init__(device)
+        self.cone_half_angle = 50.0                  # sbtmdosrenderer.cpp:37-43
+        self.evaluate_dir_occlusion = True
+        self.grid_size = (2, 2)
+        self.max_number_of_passes = 90000
+        self.occ_ui_weight_percentage = 1.0
+        self.z_near, self.z_far = 1.0, 5000.0        # camera.cpp:27-28
+        self._params = N.SbtmParams()
+
+    def GetName(self): return "Slice-based - Directional Occlusion"
+    def GetAbbreviationName(self): return "s_sbtm_dos"
+
+    @property
+    def number_of_passes(self) -> int:
+        """Slices drawn by the last Redraw ("Number of passes" of the reference's UI)."""
+        return int(N.lib().cvr_get_option(self.device.handle, b"sbtm_slices"))
+
+    def Update(self, camera: Camera) -> bool:
+        self._frame = self._camera_frame(camera)
+        p = self._params
+        p.step = float(self.m_u_step_size)
+        p.cone_half_angle_deg = float(self.cone_half_angle)
+        p.grid_x, p.grid_y = (int(v) for v in self.grid_size)
+        p.attenuation = float(self.occ_ui_weight_percentage)
+        p.max_passes = int(self.max_number_of_passes)
+        p.z_near, p.z_far = float(self.z_near), float(self.z_far)
+        return True
+
+    _ENTRY = "cvr_render_sbtm"
+
+
 def build_crtgt_rays(occ_aperture_deg: float, n_occ: int, sdw_aperture_deg: float, n_sdw: int,
                      seed: int = 1):
     """The ground-truth renderer's two ray tables (cvr_crtgt_build_rays: one minstd_rand0

@@ -726,6 +726,66 @@ cvr_status  cvr_vct_read_table(cvr_ctx* ctx, float* out);
 cvr_status  cvr_render_vct(cvr_ctx* ctx, const cvr_frame* frame, const cvr_vct_params* params,
                            const cvr_output* out);
 
+/* ----------------------------------------------------------------------------
+ * Slice-based directional occlusion (SBTMDirectionalOcclusionShading, "Slice-based -
+ * Directional Occlusion", s_sbtm_dos: structured/sbtmdos/sbtmdosrenderer.cpp,
+ * evaluationslice.vert / .frag).  Schott et al.'s original algorithm, of which
+ * cvr_render_dosct, cvr_render_extbsd and cvr_render_vct are the ray-casting
+ * approximations: view-aligned slices front to back, each a 2-D pass over the
+ * screen that composites its sample into an RGBA16F eye buffer, weighted by an
+ * occlusion buffer, and writes the next occlusion buffer as the mean of grid_x x
+ * grid_y bilinear taps of the previous one inside the cone's footprint, attenuated
+ * by the sample's extinction (DESIGN.md 5d''' holds the arithmetic).  The reference
+ * rasterises the slices; here every fragment is the point of its pixel's view ray
+ * at the slice's depth, so a slice is a kernel over the screen.
+ *
+ * Reproduced as written: every slice is drawn with slice 0's quad moved by
+ * cam_dir * pos_from_near, so it lies half a first step deeper than its own centre;
+ * the quad's half side is the volume diagonal in voxels, unscaled, so a scaled
+ * volume can stick out of it; a pixel whose fragment is discarded keeps, in the
+ * occlusion buffer being written, the value of two slices earlier, which its
+ * neighbours then read; a slice outside [z_near, z_far] is a pass that discards
+ * every fragment; a camera looking along (0, 1, 0) has a NaN quad and a transparent
+ * black frame.  No early ray termination, no light, no gradient.
+ *
+ * The pixels of a frame depend on their neighbours, so a frame is whole: screen
+ * tiles (cvr_frame nranks > 1) and group contexts (cvr_create_group), which would
+ * cut the screen into independent shares, return CVR_ERR_ARG.  Honours filter_bits (the
+ * volume, TF and occlusion-buffer fetches); with native_exp set the call returns
+ * CVR_ERR_ARG.  Device memory, counted by cvr_device_bytes from the first frame to
+ * the next volume or transfer function: 16 B per pixel (the RGBA16F eye buffer and
+ * two sets of the two R16F occlusion buffers: a launch of several slices reads one
+ * set and writes the other).
+ *
+ * Options: "sbtm_slices_per_launch" (1..16): slices one kernel launch advances with
+ * the occlusion buffers of its screen tile and a halo in LDS; a batch whose halo
+ * does not fit runs one launch per slice.  Every value gives the same bits.
+ * Read-only after a frame: "sbtm_slices" (slices drawn) and "sbtm_launches" (slice
+ * kernel launches).
+ * -------------------------------------------------------------------------- */
+#define CVR_SBTM_MAX_GRID 16          /* taps per axis                                 */
+#define CVR_SBTM_MAX_SLICES 1000000   /* slices the step may cut [minimum_z, maximum_z] into */
+typedef struct cvr_sbtm_params {
+  float step;                  /* <= 0: 0.5/sqrt(3)*|scale| (sbtmdosrenderer.cpp:112)   */
+  float cone_half_angle_deg;   /* cone_half_angle (50, in (0, 90))                      */
+  int   grid_x, grid_y;        /* grid_size (2 x 2, in [1, CVR_SBTM_MAX_GRID])          */
+  float attenuation;           /* occ_ui_weight_percentage (1.0, in [0, 1])             */
+  int   max_passes;            /* max_number_of_passes (90000, >= 0)                    */
+  float z_near, z_far;         /* the camera's clip planes (1, 5000; 0 < near <= far)   */
+} cvr_sbtm_params;
+void        cvr_sbtm_params_default(cvr_sbtm_params* out);
+/* One frame.  samples: per pixel, the fragments kept (neither clipped nor
+ * discarded); total: their sum.  CVR_ERR_STATE without a volume or a TF;
+ * CVR_ERR_ARG for a parameter out of its range, a step that cannot advance a float
+ * at maximum_z or cuts more than CVR_SBTM_MAX_SLICES slices, and screen tiles. */
+cvr_status  cvr_render_sbtm(cvr_ctx* ctx, const cvr_frame* frame, const cvr_sbtm_params* params,
+                            const cvr_output* out);
+/* The two occlusion buffers as the last frame left them: 2 planes of width x height
+ * floats (the stored binary16 values widened), plane 0 first; blocks.  CVR_ERR_STATE
+ * without a frame since the last volume or transfer function, CVR_ERR_ARG when width x
+ * height is not that frame's viewport. */
+cvr_status  cvr_sbtm_read_occlusion(cvr_ctx* ctx, int width, int height, float* out);
+
 /* The reference renderers' default parameters for `variant`. */
 void        cvr_iso_params_default(int variant, cvr_iso_params* out);
 /* One isosurface frame (first hits composited front to back with Color).  The

@@ -445,6 +445,50 @@ cvr_status HipVoxelConeTracingSGPU::RenderFrame (const cvr_output* out)
 }
 
 ////////////////////////////////////////////////////////////////////////////////
+// SBTMDirectionalOcclusionShading (sbtmdosrenderer.cpp:20-174)
+////////////////////////////////////////////////////////////////////////////////
+HipSBTMDirectionalOcclusionShading::HipSBTMDirectionalOcclusionShading ()
+  : m_u_step_size(0.5f)
+  , cone_half_angle(50.0f)                     // sbtmdosrenderer.cpp:37-43
+  , evaluate_dir_occlusion(true)
+  , grid_size(2.0f)
+  , max_number_of_passes(90000)
+  , occ_ui_weight_percentage(1.0f)
+  , m_params()
+{
+  cvr_sbtm_params_default(&m_params);
+}
+
+bool HipSBTMDirectionalOcclusionShading::Init (int swidth, int sheight)
+{
+  if (IsBuilt()) Clean();
+  if (m_ext_data_manager->GetCurrentVolumeTexture() == nullptr) return false;
+  if (!UploadVolume() || !UploadTransferFunction()) return false;
+  m_u_step_size = DefaultStep();                                               // :111-112
+  Reshape(swidth, sheight);
+  SetBuilt(true);
+  SetOutdated();
+  return true;
+}
+
+bool HipSBTMDirectionalOcclusionShading::Update (vis::Camera* camera)
+{
+  FillFrame(camera);
+  m_params.step = m_u_step_size;
+  m_params.cone_half_angle_deg = cone_half_angle;
+  m_params.grid_x = (int)grid_size.x;
+  m_params.grid_y = (int)grid_size.y;
+  m_params.attenuation = occ_ui_weight_percentage;
+  m_params.max_passes = max_number_of_passes;
+  return true;
+}
+
+cvr_status HipSBTMDirectionalOcclusionShading::RenderFrame (const cvr_output* out)
+{
+  return cvr_render_sbtm(m_cvr, &frame_, &m_params, out);
+}
+
+////////////////////////////////////////////////////////////////////////////////
 // The isosurface ray-casters (rc1pisoadapt, rc1pisocustom, rc1pisodfscustom)
 ////////////////////////////////////////////////////////////////////////////////
 HipIsoRayCasterBase::HipIsoRayCasterBase (int variant)

@@ -10,6 +10,8 @@
  *   HipRC1PConeLightGroundTruthSteps <- RC1PConeLightGroundTruthSteps
  *   HipVoxelConeTracingSGPU          <- RC1PVoxelConeTracingSGPU
  *                                                              (rc1pcrtgt/crtgtrenderer.h:50-118)
+ *   HipSBTMDirectionalOcclusionShading <- SBTMDirectionalOcclusionShading
+ *                                                              (sbtmdos/sbtmdosrenderer.h)
  *   HipRayCasting1PassIsoAdapt       <- RayCasting1PassIsoAdapt (rc1pisoadapt/rc1pisoadaptrenderer.h)
  *   HipCustomRayCasting1PassIsoAdapt <- CustomRayCasting1PassIsoAdapt (rc1pisocustom/...)
  *   HipCustomRayCasting1PassIsodfsAdapt <- CustomRayCasting1PassIsodfsAdapt (rc1pisodfscustom/...)
@@ -182,6 +184,31 @@ protected:
   cvr_status RenderFrame (const cvr_output* out) override;
   bool UploadOpacities ();             // GetOpc(i, 255) for the pre-integration table
   cvr_vct_params m_params;
+};
+
+// Schott et al.'s slice-based directional occlusion: view-aligned slices composited
+// through an eye buffer and two occlusion buffers (cvr_render_sbtm).  No light, no
+// gradient; whole frames only.
+class HipSBTMDirectionalOcclusionShading : public HipRendererBase
+{
+public:
+  HipSBTMDirectionalOcclusionShading ();
+  const char* GetName () override { return "Slice-based - Directional Occlusion (HIP, MI355X)"; }
+  const char* GetAbbreviationName () override { return "s_sbtm_dos_hip"; }
+  bool Init (int shader_width, int shader_height) override;
+  bool Update (vis::Camera* camera) override;
+
+  // sbtmdosrenderer.cpp:20-48
+  float m_u_step_size;
+  float cone_half_angle;
+  bool evaluate_dir_occlusion;
+  glm::vec2 grid_size;
+  int max_number_of_passes;
+  float occ_ui_weight_percentage;
+
+protected:
+  cvr_status RenderFrame (const cvr_output* out) override;
+  cvr_sbtm_params m_params;
 };
 
 // The three single-pass isosurface ray-casters share one library entry point

@@ -2,7 +2,7 @@
 """How far the approximate lighting paths are from the ground truth (DESIGN.md §5d′, §5d″).
 
 On the bench scene at a reduced size (Marschner-Lobb --size^3 -> --res^2, the bonsai
-TF, the "Initial State" camera, light 0 of the reference's list) five frames are taken
+TF, the "Initial State" camera, light 0 of the reference's list) six frames are taken
 on one GPU:
 
   * the ground truth: cvr_render_crtgt with --rays secondary rays per term, the
@@ -12,7 +12,9 @@ on one GPU:
   * cvr_render_dosct            (cone occlusion + point-light cone shadow, on the fly);
   * cvr_render_dosct_preillum   (the same through a 32^3 light cache);
   * cvr_render_extbsd           (SAT occlusion + point-light SAT shadow);
-  * cvr_render_vct              (voxel cone tracing shadow, the reference's defaults).
+  * cvr_render_vct              (voxel cone tracing shadow, the reference's defaults);
+  * cvr_render_sbtm             (slice-based directional occlusion, the reference's defaults:
+                                 occlusion toward the eye only, no light term).
 
 Prints the SSIM of each against the ground truth (cpp_volume_rendering_amd/ssim.py: the
 frames as screenshots over white) and the ground truth's time per frame, as a table and
@@ -34,8 +36,8 @@ from cpp_volume_rendering_amd.renderer import (Camera, DataManager,  # noqa: E40
                                                RC1PConeLightGroundTruthSteps,
                                                RC1PConeTracingDirOcclusionShading,
                                                RC1PExtinctionBasedShading, RC1PVoxelConeTracingSGPU,
-                                               RenderingParameters, build_ext_lut, build_opacity_lut,
-                                               build_tf_rgbt)
+                                               RenderingParameters, SBTMDirectionalOcclusionShading,
+                                               build_ext_lut, build_opacity_lut, build_tf_rgbt)
 from cpp_volume_rendering_amd.ssim import ssim_rgba  # noqa: E402
 
 
@@ -91,7 +93,8 @@ def main():
 
     for name, r in (("cvr_render_dosct", dos(False)), ("cvr_render_dosct_preillum", dos(True)),
                     ("cvr_render_extbsd", RC1PExtinctionBasedShading(0)),
-                    ("cvr_render_vct", RC1PVoxelConeTracingSGPU(0))):
+                    ("cvr_render_vct", RC1PVoxelConeTracingSGPU(0)),
+                    ("cvr_render_sbtm", SBTMDirectionalOcclusionShading(0))):
         r.SetExternalResources(dm, rp)
         assert r.Init(W, W)
         res["ssim"][name] = ssim_rgba(frame_of(r, cam), truth)
