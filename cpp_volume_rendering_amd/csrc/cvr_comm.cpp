@@ -559,6 +559,31 @@ cvr_status cvr_gather_tiles_n(cvr_ctx* ctx, const cvr_frame* f, int nframes, con
   const long long g = m->ngather;
   const int B = buffer_sets(c);
   const int set = (int)(g % B);
+  const int D = std::max(c->split_streams, 1);
+  const long long w = g + D - B;   // the exchange whose buffers this stream's next render reuses
+  // The in-process transport's order is checked before anything is committed: a
+  // refused call leaves ngather, the ring and the peers' view of this rank as they
+  // were, so the caller can issue the exchange again in the right order.
+  hipEvent_t ev_reuse = nullptr;
+  if (m->hub && m->rank == 0) {
+    for (int r = 1; r < m->nranks; r++) {
+      const Ctx* cr = m->hub->ctxs[(size_t)r];   // (null: that member has left)
+      const Comm* mr = cr ? comm_of(cr) : nullptr;
+      if (!mr || mr->ngather <= g)
+        return cfail(c, CVR_ERR_STATE,
+                     "local exchange %lld: rank %d has not issued it (call ranks 1..N-1 "
+                     "before rank 0)", g, r);
+      const Pending& Pr = mr->pend[g % kRing];
+      if (code && (!Pr.code || cvr::tile_code_bound_bytes(Pr.f.tile_size, Pr.tpr * Pr.nframes) >
+                                   cvr::tile_code_bound_bytes(f->tile_size, tpr_max * nframes)))
+        return cfail(c, CVR_ERR_STATE,
+                     "local exchange %lld: rank %d's group (%d frames of %d tiles) does not fit "
+                     "rank 0's slot (%d frames of %d tiles)", g, r, Pr.nframes, Pr.tpr, nframes,
+                     tpr_max);
+    }
+  } else if (m->hub && w >= 0) {
+    CTRY(reuse_event(c, m, w, &ev_reuse));   // (reads rank 0's count only)
+  }
   // the ring of pending exchanges must not overrun unposted entries
   if (g - m->nposted >= kRing) CTRY(post_through(c, m, g - kRing));
   Pending& P = m->pend[g % kRing];
@@ -620,12 +645,9 @@ cvr_status cvr_gather_tiles_n(cvr_ctx* ctx, const cvr_frame* f, int nframes, con
   // last used by exchange g + D - B, so the stream waits for that one -- with
   // B = D this exchange, with B = 4D one issued three rounds earlier, which has
   // usually finished, so a slow exchange no longer stalls the render pipeline.
-  const int D = std::max(c->split_streams, 1);
-  const long long w = g + D - B;
   if (w >= 0) {
-    hipEvent_t ev = nullptr;
-    CTRY(reuse_event(c, m, w, &ev));
-    CHIP(c, hipStreamWaitEvent(s, ev, 0));
+    if (!ev_reuse) CTRY(reuse_event(c, m, w, &ev_reuse));
+    CHIP(c, hipStreamWaitEvent(s, ev_reuse, 0));
   }
   return CVR_OK;
 }

@@ -938,7 +938,10 @@ cvr_status  cvr_gather_tiles(cvr_ctx* ctx, const cvr_frame* frame, const void* d
  * collectives: a gather's host and launch cost is shared by nframes frames).
  * `frame` gives the tile layout (the camera is not used).  Rank 0's
  * `d_gathered` holds nranks blocks of nframes * tiles_per_rank_max tiles, and
- * frame j is unpacked into d_images[j] (in frame order; NULL skips it). */
+ * frame j is unpacked into d_images[j] (in frame order; NULL skips it).
+ * A call that returns CVR_ERR_ARG or CVR_ERR_STATE has issued no exchange: this
+ * rank's exchange count, its buffers and images, and what the other ranks see of
+ * it are as before the call, so the same exchange can be issued again. */
 cvr_status  cvr_gather_tiles_n(cvr_ctx* ctx, const cvr_frame* frame, int nframes,
                                const void* d_packed, int tiles_per_rank_max, int format,
                                void* d_gathered, void* const* d_images);
