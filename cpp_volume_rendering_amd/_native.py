@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = (
     "cvr_vct_params_default", "cvr_tf1d_opacity_lut", "cvr_vct_set_opacity", "cvr_vct_precompute",
     "cvr_vct_info", "cvr_vct_read_pyramid", "cvr_vct_read_table", "cvr_render_vct",
     "cvr_sbtm_params_default", "cvr_render_sbtm", "cvr_sbtm_read_occlusion",
+    "cvr_deferred_params_default", "cvr_render_deferred", "cvr_deferred_geometry", "cvr_deferred_shade",
+    "cvr_deferred_read_gbuffer",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
     "cvr_decode_tiles", "cvr_comm_init_local", "cvr_create_group", "cvr_group_size",
@@ -160,6 +162,16 @@ class VctParams(ctypes.Structure):
                 ("cone_initial_step", ctypes.c_float), ("cone_apex_angle_deg", ctypes.c_float),
                 ("apply_correction", ctypes.c_int), ("correction_factor", ctypes.c_float),
                 ("samples", ctypes.c_int)]
+
+
+class DeferredParams(ctypes.Structure):
+    """cvr_deferred_params (include/cvr.h)."""
+    _fields_ = [("isovalue", ctypes.c_float), ("step_small", ctypes.c_float), ("step_large", ctypes.c_float),
+                ("step_range", ctypes.c_float), ("num_blocks", ctypes.c_int * 3), ("color", ctypes.c_float * 4),
+                ("ka", ctypes.c_float), ("kd", ctypes.c_float), ("ks", ctypes.c_float),
+                ("shininess", ctypes.c_float), ("light_color", ctypes.c_float * 3),
+                ("light_pos", ctypes.c_float * 3), ("exposure", ctypes.c_float), ("gamma", ctypes.c_float),
+                ("gbuffer_clear", ctypes.c_float * 4)]
 
 
 class SbtmParams(ctypes.Structure):
@@ -301,6 +313,12 @@ def lib() -> ctypes.CDLL:
         "cvr_render_sbtm": ([P, ctypes.POINTER(Frame), ctypes.POINTER(SbtmParams),
                              ctypes.POINTER(Output)], I),
         "cvr_sbtm_read_occlusion": ([P, I, I, FP], I),
+        "cvr_deferred_params_default": ([ctypes.POINTER(DeferredParams)], None),
+        "cvr_render_deferred": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DeferredParams),
+                                 ctypes.POINTER(Output)], I),
+        "cvr_deferred_geometry": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DeferredParams)], I),
+        "cvr_deferred_shade": ([P, I, I, ctypes.POINTER(DeferredParams), ctypes.POINTER(Output)], I),
+        "cvr_deferred_read_gbuffer": ([P, I, I, FP, FP], I),
         "cvr_iso_params_default": ([I, ctypes.POINTER(IsoParams)], None),
         "cvr_render_iso": ([P, ctypes.POINTER(Frame), ctypes.POINTER(IsoParams),
                             ctypes.POINTER(Output)], I),

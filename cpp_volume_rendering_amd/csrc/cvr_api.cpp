@@ -104,6 +104,7 @@ static void derived_drop(Ctx* c, Changed what) {
   vct_drop(c, volume_gone);
   sbtm_drop(c);
   if (volume_gone) iso_drop(c);
+  if (volume_gone) deferred_drop(c, destroy);
 }
 
 static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, int bpv, int w,
@@ -361,7 +362,7 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
     return b;
   }
   return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
-         c->lc.bytes + c->gt.bytes + c->vct.bytes + c->sbtm.bytes;
+         c->lc.bytes + c->gt.bytes + c->vct.bytes + c->sbtm.bytes + c->deferred.bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {

@@ -1,6 +1,6 @@
 // cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
 // cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_crtgt.cpp,
-// cvr_vct.cpp, cvr_sbtm.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
+// cvr_vct.cpp, cvr_sbtm.cpp, cvr_deferred.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
 // the host arithmetic, and the frame set-up common to the renderers.  Host only:
 // never included by a .hip file or a kernel header.
 //
@@ -141,6 +141,13 @@ void sat_drop(Ctx* c, int parts = kSatAll);
 // the context's end also destroys its event
 void light_cache_drop(Ctx* c, bool destroy = false);
 void iso_drop(Ctx* c);   // cvr_iso.cpp: the block table
+// cvr_iso.cpp: the block min/max table of the context's volume for nb blocks per axis
+// (ComputeBlocksFromVolume; the iso renderers' and DeferredShading's are one function),
+// built when the volume or nb changed; blocks
+cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]);
+// cvr_deferred.cpp: the G-buffer goes with the volume (and with another viewport);
+// the context's end also frees its hit counter
+void deferred_drop(Ctx* c, bool destroy = false);
 
 // cvr_crtgt.cpp: a new volume, TF or gradient ends the ground-truth frame in
 // progress; the context's end frees its state

@@ -293,6 +293,20 @@ struct IsoArgs {
   float color[4];
 };
 
+// Deferred isosurface shading (deferred.hip).  The G-buffer is two float4 planes of
+// W x H, gPosition then gNormal.  gNormal.w always equals gPosition.w (hit: 1, in-box
+// miss: 0, off the box: the clear value's w), so its slot holds the pixel's fetch
+// count instead (uint32 bits; 0 exactly off the box) and readers take w from gPosition.
+struct DeferredShadeArgs {           // lighting_pass.comp's and post_process.frag's uniforms
+  int W, H;
+  float eye[3];                      // CameraEye of the kept frame
+  float light[3];                    // LightSourcePosition
+  float light_color[3];
+  float color[4];                    // objectColor
+  float ka, kd, ks, shininess;
+  float exposure, gamma;
+};
+
 // Several frames in one ray-march launch (cvr_render_rc1pass_frames): frame f
 // takes workgroups [f * grid, (f + 1) * grid) and differs from frame 0 only in
 // its view (camera) and its outputs.  grid is a multiple of 8 whenever the
@@ -589,6 +603,19 @@ struct Ctx {
     int slices = 0, launches = 0;
   } sbtm;
   int sbtm_slices_per_launch = 1;    // option "sbtm_slices_per_launch" (default: by measurement, DESIGN.md 5d''')
+  // deferred isosurface shading (cvr_deferred.cpp): the G-buffer of the last geometry
+  // pass (DeferredShadeArgs above: 32 B per pixel), the viewport and camera eye of that
+  // pass, its hit counter on the device (option "deferred_hits") and the geometry
+  // launches so far (option "deferred_launches")
+  struct Deferred {
+    float4* d_gbuf = nullptr;          // gPosition at [0, npix), gNormal at [npix, 2 npix)
+    unsigned long long* d_hits = nullptr;
+    int W = 0, H = 0;
+    bool valid = false;                // a geometry pass has filled it
+    float eye[3] = {0, 0, 0};
+    size_t bytes = 0;                  // the planes (cvr_device_bytes)
+    int launches = 0;
+  } deferred;
   unsigned long long* d_tile_samples = nullptr;   // per-wave-tile sample counts (zeroed)
   int tile_samples_n = 0;
   // d_tile_samples and d_shade are one set per context: a frame that uses them on
@@ -712,6 +739,13 @@ hipError_t launch_block_minmax(const void* vox, int bpv, const int N[3], const i
 hipError_t launch_iso(const Ctx& c, const IsoArgs& q, int variant, bool phong, const float2* mm,
                       float4* out, uint32_t* samples, unsigned long long* tile_samples,
                       hipStream_t s);
+// deferred.hip: the geometry pass (q: the iso march's uniforms; clear: the G-buffer's
+// clear value; hits: += pixels with a hit) and the shade pass over a G-buffer (lighting
+// and tone map; samples / total: the geometry pass's counts, total is added to)
+hipError_t launch_deferred_geometry(const Ctx& c, const IsoArgs& q, const float clear[4], const float2* mm,
+                                    float4* gbuf, unsigned long long* hits, hipStream_t s);
+hipError_t launch_deferred_shade(const DeferredShadeArgs& q, const float4* gbuf, float4* out, int half,
+                                 uint32_t* samples, unsigned long long* total, hipStream_t s);
 // codec.hip: the lossless per-tile code of RGBA16F tiles (cvr_encode_tiles)
 size_t tile_code_bound_bytes(int tile, int ntiles);
 hipError_t launch_tile_encode(const void* d_tiles, int tile, int ntiles, void* d_stream,

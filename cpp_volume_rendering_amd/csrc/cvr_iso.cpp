@@ -20,7 +20,7 @@ void cvr::iso_drop(Ctx* c) {
 // The block table for nb: raw extremes on the GPU, normalised here exactly as
 // ComputeBlocksFromVolume stores them (v / 255 or v / 65535 in double, pushed
 // into a float vector; empty blocks keep numeric_limits<float>::max / lowest).
-static cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]) {
+cvr_status cvr::ensure_iso_blocks(Ctx* c, const int nb[3]) {
   if (c->iso.valid && c->iso.d_mm && c->iso.nb[0] == nb[0] && c->iso.nb[1] == nb[1] &&
       c->iso.nb[2] == nb[2])
     return CVR_OK;
@@ -33,7 +33,7 @@ static cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]) {
   if (e == hipSuccess) e = hipMemcpyAsync(raw.data(), d_raw, n * sizeof(uint2), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(d_raw);
-  if (e != hipSuccess) return fail(c, CVR_ERR_HIP, "cvr_render_iso: block table: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(c, CVR_ERR_HIP, "the isosurface block table: %s", hipGetErrorString(e));
   const double mx = c->bpv == 1 ? 255.0 : 65535.0;
   std::vector<float2> mm(n);
   for (size_t i = 0; i < n; i++) {

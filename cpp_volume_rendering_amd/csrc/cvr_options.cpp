@@ -156,6 +156,19 @@ const Option kOptions[] = {
     // the last slice-based frame: slices drawn, and the launches that drew them
     {"sbtm_slices", nullptr, [](const Ctx* c) { return c->sbtm.slices; }, 1, 0, nullptr, nullptr, nullptr},
     {"sbtm_launches", nullptr, [](const Ctx* c) { return c->sbtm.launches; }, 1, 0, nullptr, nullptr, nullptr},
+    // the kept G-buffer's pixels with a hit (waits for its geometry pass; -1: none kept), and
+    // the geometry launches so far
+    {"deferred_hits", nullptr,
+     [](const Ctx* c) {
+       unsigned long long n = 0;
+       if (!c->deferred.valid || hipSetDevice(c->device) != hipSuccess ||
+           hipStreamSynchronize(c->stream) != hipSuccess ||
+           hipMemcpy(&n, c->deferred.d_hits, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
+         return -1;
+       return (int)n;
+     },
+     1, 0, nullptr, nullptr, nullptr},
+    {"deferred_launches", nullptr, [](const Ctx* c) { return c->deferred.launches; }, 1, 0, nullptr, nullptr, nullptr},
 };
 
 const Option* find_option(const char* key) {

@@ -1188,6 +1188,93 @@ class CustomRayCasting1PassIsodfsAdapt(CustomRayCasting1PassIsoAdapt):
     def GetName(self): return "Empty Sapce Skipping V2"
 
 
+class DeferredShading(RayCasting1PassIsoAdapt):
+    """HIP implementation of DeferredShading
+    (cppvolrend/structured/DeferredShading/DeferredShading.cpp): a first-hit isosurface
+    march into a G-buffer (position, central-difference normal), a Blinn-Phong pass over
+    it and a tone map.  The G-buffer is kept: Update marks the geometry outdated only when
+    the camera, the volume or a march parameter changed, and Redraw then runs the shade
+    pass alone (a change of light, material, colour, exposure or gamma marches no ray).
+    A BaseVolumeRenderer through RayCasting1PassIsoAdapt, whose Init it shares."""
+
+    def __init__(self, device: int = 0):
+        RayCasting1Pass.__init__(self, device)
+        self._params = N.DeferredParams()
+        N.lib().cvr_deferred_params_default(ctypes.byref(self._params))
+        d = self._params
+        self.m_u_isovalue = d.isovalue              # DeferredShading.cpp:123-128
+        self.m_u_step_size_small = d.step_small
+        self.m_u_step_size_large = d.step_large
+        self.m_u_step_size_range = d.step_range
+        self.m_u_color = tuple(d.color)
+        self.m_apply_gradient_shading = False
+        self.num_blocks = tuple(d.num_blocks)       # Init (:348)
+        self.light_color = tuple(d.light_color)     # LightingPass (:216)
+        self.exposure, self.gamma = d.exposure, d.gamma   # Redraw (:538-539)
+        self.gbuffer_clear = tuple(d.gbuffer_clear)
+        self.vr_pixel_multiscaling_support = False
+        self._geometry_key = None                   # what the kept G-buffer was marched from
+        self._geometry_outdated = True
+
+    def GetName(self): return "Deferred Rendering"
+    def GetAbbreviationName(self): return "iso"
+
+    @property
+    def geometry_launches(self) -> int:
+        return int(N.lib().cvr_get_option(self.device.handle, b"deferred_launches"))
+
+    def Init(self, swidth: int, sheight: int) -> bool:
+        self._geometry_key = None                   # a new device: nothing kept
+        return super().Init(swidth, sheight)
+
+    def Update(self, camera: Camera) -> bool:
+        rp = self.m_ext_rendering_parameters or RenderingParameters()
+        self._frame = self._camera_frame(camera)
+        p = self._params
+        p.num_blocks[:] = [int(b) for b in self.num_blocks]
+        p.isovalue = float(self.m_u_isovalue)
+        p.step_small = float(self.m_u_step_size_small)
+        p.step_large = float(self.m_u_step_size_large)
+        p.step_range = float(self.m_u_step_size_range)
+        p.gbuffer_clear[:] = [float(c) for c in self.gbuffer_clear]
+        p.color[:] = [float(c) for c in self.m_u_color]
+        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd   # UpdateLightingPassUniforms (:477-482)
+        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
+        p.light_color[:] = [float(v) for v in self.light_color]
+        p.light_pos[:] = [float(v) for v in rp.light_position]
+        p.exposure, p.gamma = float(self.exposure), float(self.gamma)
+        f = self._frame
+        key = (bytes(f), tuple(p.num_blocks), p.isovalue, p.step_small, p.step_large, p.step_range,
+               tuple(p.gbuffer_clear), id(self._dev))
+        self._geometry_outdated = key != self._geometry_key
+        self._pending_key = key
+        return True
+
+    def render_to(self, frame: N.Frame, out: N.Output):
+        h = self.device.handle
+        if frame is self._frame and not self._geometry_outdated:
+            N.check(N.lib().cvr_deferred_shade(h, frame.width, frame.height, ctypes.byref(self._params),
+                                               ctypes.byref(out)), "cvr_deferred_shade", h)
+            return
+        self._geometry_key = None
+        N.check(N.lib().cvr_render_deferred(h, ctypes.byref(frame), ctypes.byref(self._params),
+                                            ctypes.byref(out)), "cvr_render_deferred", h)
+        if frame is self._frame:
+            self._geometry_key = self._pending_key
+            self._geometry_outdated = False
+
+    def render_frames_to(self, frames, outs):
+        raise NotImplementedError("DeferredShading: one frame per call")
+
+    def FillParameterSpace(self, pspace: dict):
+        pspace.clear()                              # DeferredShading.cpp:545-551
+        pspace["StepSizeSmall"] = (0.01, 0.25, 0.05)
+        pspace["StepSizeLarge"] = (0.25, 2.0, 0.25)
+        pspace["StepSizeRange"] = (0.05, 0.26, 0.05)
+
+    _ENTRY = "cvr_render_deferred"
+
+
 def composite_over_white(rgba: np.ndarray) -> np.ndarray:
     """Screen image as RenderFrameToScreen::Draw blends it over the white clear colour
     with SRC_ALPHA / ONE_MINUS_SRC_ALPHA (renderingmanager.cpp:103-112), as RGB8."""

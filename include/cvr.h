@@ -786,6 +786,69 @@ cvr_status  cvr_render_sbtm(cvr_ctx* ctx, const cvr_frame* frame, const cvr_sbtm
  * height is not that frame's viewport. */
 cvr_status  cvr_sbtm_read_occlusion(cvr_ctx* ctx, int width, int height, float* out);
 
+/* ----------------------------------------------------------------------------
+ * DeferredShading ("Deferred Rendering", abbreviation "iso"; cppvolrend/structured/
+ * DeferredShading): a first-hit isosurface march that stores the hit's texture-space
+ * position and central-difference normal into a G-buffer (geometry_pass.comp), a
+ * Blinn-Phong pass over the G-buffer (lighting_pass.comp) and a tone map
+ * (post_process.frag).  The G-buffer belongs to the context, so a change of light,
+ * material, colour, exposure or gamma re-shades the kept frame without marching a ray
+ * (cvr_deferred_shade).
+ *
+ * Reproduced as written: a ray that misses the box keeps the G-buffer's
+ * clear value (gbuffer_clear, the application's (1, 1, 1, 0)) and is then LIT with the
+ * unnormalised normal (1, 1, 1); normalize of a zero gradient is NaN and is stored;
+ * the lighting pass mixes the texture-space position with the world-space light and
+ * eye; it samples the G-buffer with GL_NEAREST at pixel / size, a texel edge, which for
+ * some sizes is the texel to the left or below (CVR-SPEC:
+ * clamp(int(floor(fl(fl(p / s) * s))), 0, s - 1) in float).  A lane stops after 2^22
+ * iterations (iso.hip's deviation).
+ *
+ * A pixel may read its neighbour's G-buffer texel, so a frame is whole: screen tiles
+ * (cvr_frame nranks > 1) and group contexts return CVR_ERR_ARG.  Device memory, counted
+ * by cvr_device_bytes from the first geometry pass to the next volume: 32 B per pixel.
+ * Read-only options: "deferred_hits" (pixels with a hit in the last geometry pass;
+ * reading it waits for that pass) and "deferred_launches" (geometry launches so far).
+ * -------------------------------------------------------------------------- */
+typedef struct cvr_deferred_params {
+  float isovalue;              /* m_u_isovalue 0.5                                       */
+  float step_small;            /* m_u_step_size_small 0.05 (> 0)                          */
+  float step_large;            /* m_u_step_size_large 1.0 (> 0)                           */
+  float step_range;            /* m_u_step_size_range 0.1 (> 0)                           */
+  int   num_blocks[3];         /* numBlocks (4, 4, 4), DeferredShading.cpp:348; 1..1024   */
+  float color[4];              /* m_u_color (0.66, 0.6, 0.05, 1.0): objectColor           */
+  float ka, kd, ks, shininess; /* the values Update binds (renderingparameters.cpp:23-26:
+                                  0.5, 0.5, 0.8, 30); LightingPass's 0.1 / 0.7 / 0.2 / 32
+                                  are stored after the last BindUniforms and never bound  */
+  float light_color[3];        /* lightColor (1, 1, 1), bound from the second Update on   */
+  float light_pos[3];          /* LightSourcePosition (light 0 of the reference's list)   */
+  float exposure;              /* 1.0 (Redraw); <= 0: no exposure map                     */
+  float gamma;                 /* 2.2 (Redraw); <= 0: no gamma map                        */
+  float gbuffer_clear[4];      /* glClear's colour (1, 1, 1, 0), renderingmanager.cpp:108 */
+} cvr_deferred_params;
+void        cvr_deferred_params_default(cvr_deferred_params* out);
+/* One frame: the geometry pass, then the shade pass, on the context stream with no
+ * host synchronisation between them.  samples: per pixel, the texture(TexVolume)
+ * evaluations of the geometry pass; total: their sum.  CVR_ERR_STATE without a volume;
+ * CVR_ERR_ARG for screen tiles, a group context, a step that is not positive, a
+ * negative material, colour or light-colour term, a NaN parameter, or a block count
+ * outside 1..1024. */
+cvr_status  cvr_render_deferred(cvr_ctx* ctx, const cvr_frame* frame, const cvr_deferred_params* params,
+                                const cvr_output* out);
+/* The geometry pass alone: marches `frame` and keeps the G-buffer (asynchronous). */
+cvr_status  cvr_deferred_geometry(cvr_ctx* ctx, const cvr_frame* frame, const cvr_deferred_params* params);
+/* The shade pass alone over the kept G-buffer (the relight path): only the lighting,
+ * material, colour and tone-map fields of `params` are read; the camera eye is the kept
+ * frame's; samples and total are the kept geometry pass's.  The output's size is the
+ * G-buffer's: width x height pixels.  CVR_ERR_STATE without a G-buffer, CVR_ERR_ARG
+ * when width x height is not its viewport. */
+cvr_status  cvr_deferred_shade(cvr_ctx* ctx, int width, int height, const cvr_deferred_params* params,
+                               const cvr_output* out);
+/* gPosition and gNormal of the kept G-buffer, width x height x 4 floats each; blocks.
+ * CVR_ERR_STATE without a G-buffer, CVR_ERR_ARG for another viewport. */
+cvr_status  cvr_deferred_read_gbuffer(cvr_ctx* ctx, int width, int height, float* out_position,
+                                      float* out_normal);
+
 /* The reference renderers' default parameters for `variant`. */
 void        cvr_iso_params_default(int variant, cvr_iso_params* out);
 /* One isosurface frame (first hits composited front to back with Color).  The

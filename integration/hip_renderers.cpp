@@ -5,6 +5,7 @@
 #include <volvis_utils/structuredgridvolume.h>
 #include <volvis_utils/transferfunction.h>
 
+#include <cstring>
 #include <vector>
 
 // Blinn-Phong constants and the light of RenderingParameters
@@ -538,6 +539,89 @@ cvr_status HipIsoRayCasterBase::RenderFrame (const cvr_output* out)
 
 // rc1custompisoadaptrenderer.cpp:349-355
 void HipIsoRayCasterBase::FillParameterSpace (ParameterSpace& pspace)
+{
+  pspace.ClearParameterDimensions();
+  pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeSmall", &m_u_step_size_small, 0.01f, 0.25f, 0.05f));
+  pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeLarge", &m_u_step_size_large, 0.25f, 2.0f, 0.25f));
+  pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeRange", &m_u_step_size_range, 0.05f, 0.26f, 0.05f));
+}
+
+////////////////////////////////////////////////////////////////////////////////
+// DeferredShading (DeferredShading.cpp:118-131, 322-551)
+////////////////////////////////////////////////////////////////////////////////
+HipDeferredShading::HipDeferredShading ()
+  : m_u_isovalue(0.5f)                 // DeferredShading.cpp:123-128
+  , m_u_step_size_small(0.05f)
+  , m_u_step_size_large(1.0f)
+  , m_u_step_size_range(0.1f)
+  , m_u_color(0.66f, 0.6f, 0.05f, 1.0f)
+  , m_apply_gradient_shading(false)
+  , m_params()
+  , m_kept_frame()
+  , m_kept_params()
+  , m_geometry_kept(false)
+{
+  cvr_deferred_params_default(&m_params);
+}
+
+// No transfer function and no gradient texture: the normal is the shader's own central
+// difference.  The block table (ComputeBlocksFromVolume, :20-113) is the library's.
+bool HipDeferredShading::Init (int swidth, int sheight)
+{
+  if (IsBuilt()) Clean();
+  if (m_ext_data_manager->GetCurrentVolumeTexture() == nullptr) return false;
+  if (!UploadVolume()) return false;
+  m_geometry_kept = false;
+  Reshape(swidth, sheight);
+  SetBuilt(true);
+  SetOutdated();
+  return true;
+}
+
+// UpdateGeometryPassUniforms / UpdateLightingPassUniforms (:447-484).  fill_phong's
+// BlinnPhongIspecular is no uniform of lighting_pass.comp.
+bool HipDeferredShading::Update (vis::Camera* camera)
+{
+  vis::RenderingParameters* rp = m_ext_rendering_parameters;
+  FillFrame(camera);
+  m_params.isovalue = m_u_isovalue;
+  m_params.step_small = m_u_step_size_small;
+  m_params.step_large = m_u_step_size_large;
+  m_params.step_range = m_u_step_size_range;
+  for (int i = 0; i < 4; i++) m_params.color[i] = m_u_color[i];
+  m_params.ka = rp->GetBlinnPhongKambient();
+  m_params.kd = rp->GetBlinnPhongKdiffuse();
+  m_params.ks = rp->GetBlinnPhongKspecular();
+  m_params.shininess = rp->GetBlinnPhongNshininess();
+  copy3(m_params.light_pos, rp->GetBlinnPhongLightingPosition());
+  return true;
+}
+
+// The march parameters of two parameter blocks are the same
+static bool same_geometry (const cvr_deferred_params& a, const cvr_deferred_params& b)
+{
+  return a.isovalue == b.isovalue && a.step_small == b.step_small && a.step_large == b.step_large &&
+         a.step_range == b.step_range && !std::memcmp(a.num_blocks, b.num_blocks, sizeof(a.num_blocks)) &&
+         !std::memcmp(a.gbuffer_clear, b.gbuffer_clear, sizeof(a.gbuffer_clear));
+}
+
+cvr_status HipDeferredShading::RenderFrame (const cvr_output* out)
+{
+  if (m_geometry_kept && !std::memcmp(&frame_, &m_kept_frame, sizeof(cvr_frame)) &&
+      same_geometry(m_params, m_kept_params))
+    return cvr_deferred_shade(m_cvr, frame_.width, frame_.height, &m_params, out);
+  m_geometry_kept = false;
+  const cvr_status st = cvr_render_deferred(m_cvr, &frame_, &m_params, out);
+  if (st == CVR_OK) {
+    m_kept_frame = frame_;
+    m_kept_params = m_params;
+    m_geometry_kept = true;
+  }
+  return st;
+}
+
+// DeferredShading.cpp:545-551
+void HipDeferredShading::FillParameterSpace (ParameterSpace& pspace)
 {
   pspace.ClearParameterDimensions();
   pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeSmall", &m_u_step_size_small, 0.01f, 0.25f, 0.05f));

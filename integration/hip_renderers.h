@@ -12,6 +12,7 @@
  *                                                              (rc1pcrtgt/crtgtrenderer.h:50-118)
  *   HipSBTMDirectionalOcclusionShading <- SBTMDirectionalOcclusionShading
  *                                                              (sbtmdos/sbtmdosrenderer.h)
+ *   HipDeferredShading                 <- DeferredShading      (DeferredShading/DeferredShading.h)
  *   HipRayCasting1PassIsoAdapt       <- RayCasting1PassIsoAdapt (rc1pisoadapt/rc1pisoadaptrenderer.h)
  *   HipCustomRayCasting1PassIsoAdapt <- CustomRayCasting1PassIsoAdapt (rc1pisocustom/...)
  *   HipCustomRayCasting1PassIsodfsAdapt <- CustomRayCasting1PassIsodfsAdapt (rc1pisodfscustom/...)
@@ -256,6 +257,36 @@ public:
   HipCustomRayCasting1PassIsodfsAdapt () : HipIsoRayCasterBase(1) {}
   const char* GetName () override { return "Empty Space Skipping V2 (HIP, MI355X)"; }
   const char* GetAbbreviationName () override { return "iso_hip"; }
+};
+
+// DeferredShading (DeferredShading/DeferredShading.cpp): the isosurface march into a
+// G-buffer the library keeps, the lighting pass and the tone map (cvr_render_deferred).
+// Update marches again only when the frame or a march parameter changed; otherwise
+// Redraw re-shades the kept G-buffer (cvr_deferred_shade).  Whole frames only.
+class HipDeferredShading : public HipRendererBase
+{
+public:
+  HipDeferredShading ();
+  const char* GetName () override { return "Deferred Rendering (HIP, MI355X)"; }
+  const char* GetAbbreviationName () override { return "iso_hip"; }
+  bool Init (int shader_width, int shader_height) override;
+  bool Update (vis::Camera* camera) override;
+  void FillParameterSpace (ParameterSpace& pspace) override;
+
+  // DeferredShading.cpp:123-128
+  float m_u_isovalue;
+  float m_u_step_size_small;
+  float m_u_step_size_large;
+  float m_u_step_size_range;
+  glm::vec4 m_u_color;
+  bool m_apply_gradient_shading;
+
+protected:
+  cvr_status RenderFrame (const cvr_output* out) override;
+  cvr_deferred_params m_params;
+  cvr_frame m_kept_frame;              // what the kept G-buffer was marched from
+  cvr_deferred_params m_kept_params;
+  bool m_geometry_kept;
 };
 
 // Adds every HIP renderer to the RenderingManager (register_hip_renderers.cpp;
