@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "cvr_sbtm_params_default", "cvr_render_sbtm", "cvr_sbtm_read_occlusion",
     "cvr_deferred_params_default", "cvr_render_deferred", "cvr_deferred_geometry", "cvr_deferred_shade",
     "cvr_deferred_read_gbuffer",
+    "cvr_advdeferred_params_default", "cvr_render_advdeferred", "cvr_advdeferred_curvature",
+    "cvr_advdeferred_shade", "cvr_advdeferred_read_curvature",
     "cvr_comm_unique_id", "cvr_comm_init", "cvr_comm_destroy", "cvr_gather_tiles",
     "cvr_gather_tiles_n", "cvr_unpack_tiles_device_n", "cvr_tile_code_bound", "cvr_encode_tiles",
     "cvr_decode_tiles", "cvr_comm_init_local", "cvr_create_group", "cvr_group_size",
@@ -172,6 +174,20 @@ class DeferredParams(ctypes.Structure):
                 ("shininess", ctypes.c_float), ("light_color", ctypes.c_float * 3),
                 ("light_pos", ctypes.c_float * 3), ("exposure", ctypes.c_float), ("gamma", ctypes.c_float),
                 ("gbuffer_clear", ctypes.c_float * 4)]
+
+
+class AdvDeferredParams(ctypes.Structure):
+    """cvr_advdeferred_params (include/cvr.h)."""
+    _fields_ = [("isovalue", ctypes.c_float), ("step_small", ctypes.c_float), ("step_large", ctypes.c_float),
+                ("step_range", ctypes.c_float), ("num_blocks", ctypes.c_int * 3), ("color", ctypes.c_float * 4),
+                ("ka", ctypes.c_float), ("kd", ctypes.c_float), ("ks", ctypes.c_float),
+                ("shininess", ctypes.c_float), ("light_color", ctypes.c_float * 3),
+                ("light_pos", ctypes.c_float * 3), ("exposure", ctypes.c_float), ("gamma", ctypes.c_float),
+                ("gbuffer_clear", ctypes.c_float * 4), ("flow_speed", ctypes.c_float),
+                ("flow_scale", ctypes.c_float), ("time", ctypes.c_float), ("show_ridges", ctypes.c_int),
+                ("show_valleys", ctypes.c_int), ("accessibility_strength", ctypes.c_float),
+                ("screen_size", ctypes.c_float * 2), ("colormap_s", ctypes.c_float),
+                ("colormap_v", ctypes.c_float)]
 
 
 class SbtmParams(ctypes.Structure):
@@ -319,6 +335,12 @@ def lib() -> ctypes.CDLL:
         "cvr_deferred_geometry": ([P, ctypes.POINTER(Frame), ctypes.POINTER(DeferredParams)], I),
         "cvr_deferred_shade": ([P, I, I, ctypes.POINTER(DeferredParams), ctypes.POINTER(Output)], I),
         "cvr_deferred_read_gbuffer": ([P, I, I, FP, FP], I),
+        "cvr_advdeferred_params_default": ([ctypes.POINTER(AdvDeferredParams)], None),
+        "cvr_render_advdeferred": ([P, ctypes.POINTER(Frame), ctypes.POINTER(AdvDeferredParams),
+                                    ctypes.POINTER(Output)], I),
+        "cvr_advdeferred_curvature": ([P, ctypes.POINTER(Frame), ctypes.POINTER(AdvDeferredParams)], I),
+        "cvr_advdeferred_shade": ([P, I, I, ctypes.POINTER(AdvDeferredParams), ctypes.POINTER(Output)], I),
+        "cvr_advdeferred_read_curvature": ([P, I, I, FP, FP, FP], I),
         "cvr_iso_params_default": ([I, ctypes.POINTER(IsoParams)], None),
         "cvr_render_iso": ([P, ctypes.POINTER(Frame), ctypes.POINTER(IsoParams),
                             ctypes.POINTER(Output)], I),

@@ -362,7 +362,8 @@ size_t cvr_device_bytes(const cvr_ctx* ctx) {
     return b;
   }
   return c->vox_bytes + c->cells_bytes + c->grad_bytes + (size_t)c->tf_n * 16 + c->scratch_bytes +
-         c->lc.bytes + c->gt.bytes + c->vct.bytes + c->sbtm.bytes + c->deferred.bytes;
+         c->lc.bytes + c->gt.bytes + c->vct.bytes + c->sbtm.bytes + c->deferred.bytes + c->adv.bytes +
+         c->adv.table_bytes;
 }
 
 cvr_status cvr_copy_cells(cvr_ctx* ctx, void* out, size_t capacity) {

@@ -18,11 +18,8 @@ void deferred_drop(Ctx* c, bool destroy) {
   D.valid = false;
   D.bytes = 0;
   if (destroy) free_dev(D.d_hits);
+  advdeferred_drop(c, destroy);   // the curvature planes are that G-buffer's
 }
-
-}  // namespace cvr
-
-namespace {
 
 bool any_nan(const float* v, int n) {
   for (int i = 0; i < n; i++)
@@ -34,6 +31,10 @@ bool any_negative(const float* v, int n) {
     if (v[i] < 0.0f) return true;
   return false;
 }
+
+}  // namespace cvr
+
+namespace {
 
 // What the shade pass reads of the parameters (cvr_powf is specified for x >= 0).
 cvr_status check_shade_params(Ctx* c, const char* who, const cvr_deferred_params* p) {
@@ -60,8 +61,12 @@ cvr_status check_geometry_params(Ctx* c, const char* who, const cvr_deferred_par
   return CVR_OK;
 }
 
+}  // namespace
+
+namespace cvr {
+
 // The checks of a call that marches `f`, before anything is launched or allocated.
-cvr_status check_geometry_call(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p) {
+cvr_status deferred_check_geometry_call(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p) {
   if (f->width < 1 || f->height < 1 || f->width > 32768 || f->height > 32768)
     return fail(c, CVR_ERR_ARG, "%s: bad viewport %dx%d", who, f->width, f->height);
   if (f->nranks > 1)
@@ -74,7 +79,7 @@ cvr_status check_geometry_call(Ctx* c, const char* who, const cvr_frame* f, cons
 }
 
 // The geometry pass of `f` into the context's G-buffer, on the context stream.
-cvr_status geometry_pass(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p) {
+cvr_status deferred_geometry_pass(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p) {
   HIP_TRY(c, hipSetDevice(c->device));
   cvr_status st = ensure_iso_blocks(c, p->num_blocks);
   if (st != CVR_OK) return st;
@@ -116,6 +121,7 @@ cvr_status geometry_pass(Ctx* c, const char* who, const cvr_frame* f, const cvr_
   }
   hipStream_t s = c->stream;
   D.valid = false;
+  c->adv.valid = false;   // the curvature planes were another G-buffer's
   HIP_TRY(c, hipMemsetAsync(D.d_hits, 0, sizeof(unsigned long long), s));
   HIP_TRY(c, launch_deferred_geometry(*c, Q, p->gbuffer_clear, c->iso.d_mm, D.d_gbuf, D.d_hits, s));
   for (int i = 0; i < 3; i++) D.eye[i] = Q.a.eye[i];
@@ -123,6 +129,17 @@ cvr_status geometry_pass(Ctx* c, const char* who, const cvr_frame* f, const cvr_
   D.launches++;
   return CVR_OK;
 }
+
+cvr_status deferred_check_output(Ctx* c, const char* who, const cvr_output* o) {
+  if (!o->rgba) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
+  if (o->format != CVR_FORMAT_RGBA32F && o->format != CVR_FORMAT_RGBA16F)
+    return fail(c, CVR_ERR_ARG, "%s: unknown output format %d", who, o->format);
+  return CVR_OK;
+}
+
+}  // namespace cvr
+
+namespace {
 
 // The shade pass over the kept G-buffer into `o`, through the shared frame-output path.
 cvr_status shade_pass(Ctx* c, const cvr_deferred_params* p, const cvr_output* o) {
@@ -154,13 +171,6 @@ cvr_status shade_pass(Ctx* c, const cvr_deferred_params* p, const cvr_output* o)
   });
   if (st != CVR_OK) return st;
   return frame_output_finish(c, o, fo, s);
-}
-
-cvr_status check_output(Ctx* c, const char* who, const cvr_output* o) {
-  if (!o->rgba) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  if (o->format != CVR_FORMAT_RGBA32F && o->format != CVR_FORMAT_RGBA16F)
-    return fail(c, CVR_ERR_ARG, "%s: unknown output format %d", who, o->format);
-  return CVR_OK;
 }
 
 }  // namespace
@@ -195,9 +205,9 @@ cvr_status cvr_deferred_geometry(cvr_ctx* ctx, const cvr_frame* f, const cvr_def
   const char* who = "cvr_deferred_geometry";
   if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
   if (!f || !p) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  const cvr_status st = check_geometry_call(c, who, f, p);
+  const cvr_status st = deferred_check_geometry_call(c, who, f, p);
   if (st != CVR_OK) return st;
-  return geometry_pass(c, who, f, p);
+  return deferred_geometry_pass(c, who, f, p);
 }
 
 cvr_status cvr_deferred_shade(cvr_ctx* ctx, int width, int height, const cvr_deferred_params* p,
@@ -207,7 +217,7 @@ cvr_status cvr_deferred_shade(cvr_ctx* ctx, int width, int height, const cvr_def
   const char* who = "cvr_deferred_shade";
   if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
   if (!p || !o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  cvr_status st = check_output(c, who, o);
+  cvr_status st = deferred_check_output(c, who, o);
   if (st == CVR_OK) st = check_shade_params(c, who, p);
   if (st != CVR_OK) return st;
   if (!c->deferred.valid) return fail(c, CVR_ERR_STATE, "%s: no G-buffer (cvr_deferred_geometry)", who);
@@ -223,11 +233,11 @@ cvr_status cvr_render_deferred(cvr_ctx* ctx, const cvr_frame* f, const cvr_defer
   const char* who = "cvr_render_deferred";
   if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
   if (!f || !p || !o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  cvr_status st = check_output(c, who, o);
+  cvr_status st = deferred_check_output(c, who, o);
   if (st == CVR_OK) st = check_shade_params(c, who, p);
-  if (st == CVR_OK) st = check_geometry_call(c, who, f, p);
+  if (st == CVR_OK) st = deferred_check_geometry_call(c, who, f, p);
   if (st != CVR_OK) return st;
-  st = geometry_pass(c, who, f, p);
+  st = deferred_geometry_pass(c, who, f, p);
   if (st != CVR_OK) return st;
   return shade_pass(c, p, o);
 }

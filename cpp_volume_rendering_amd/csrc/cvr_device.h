@@ -212,6 +212,9 @@ __device__ __forceinline__ float sqrt_cr_normal(float x) {
 }
 
 __device__ __forceinline__ float dot3(f3 a, f3 b) { return fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)); }
+__device__ __forceinline__ f3 cross3(f3 x, f3 y) {   // glm / GLSL cross, no fma
+  return f3{x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y};
+}
 // normalize(v) = v * RN(1 / RN(sqrt(dot(v, v)))) (CVR-SPEC): the short exact
 // sequence when dot(v, v) lies in [2^-96, 2^126), else the IEEE operators.
 __device__ __forceinline__ f3 normalize3(f3 v) {

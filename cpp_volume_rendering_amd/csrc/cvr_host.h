@@ -1,6 +1,6 @@
 // cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
 // cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_crtgt.cpp,
-// cvr_vct.cpp, cvr_sbtm.cpp, cvr_deferred.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
+// cvr_vct.cpp, cvr_sbtm.cpp, cvr_deferred.cpp, cvr_advdeferred.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
 // the host arithmetic, and the frame set-up common to the renderers.  Host only:
 // never included by a .hip file or a kernel header.
 //
@@ -148,6 +148,17 @@ cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]);
 // cvr_deferred.cpp: the G-buffer goes with the volume (and with another viewport);
 // the context's end also frees its hit counter
 void deferred_drop(Ctx* c, bool destroy = false);
+// cvr_deferred.cpp, for the renderers over its G-buffer (cvr_advdeferred.cpp): the
+// checks of a call that marches `f`, the geometry pass into the context's G-buffer on
+// the context stream, and the check of an output's buffer and format
+bool any_nan(const float* v, int n);
+bool any_negative(const float* v, int n);
+cvr_status deferred_check_geometry_call(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p);
+cvr_status deferred_geometry_pass(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p);
+cvr_status deferred_check_output(Ctx* c, const char* who, const cvr_output* o);
+// cvr_advdeferred.cpp: the curvature planes go with the G-buffer (deferred_drop calls
+// this); the context's end also frees the lighting pass's tables and its counter
+void advdeferred_drop(Ctx* c, bool destroy = false);
 
 // cvr_crtgt.cpp: a new volume, TF or gradient ends the ground-truth frame in
 // progress; the context's end frees its state

@@ -307,6 +307,24 @@ struct DeferredShadeArgs {           // lighting_pass.comp's and post_process.fr
   float exposure, gamma;
 };
 
+// Advanced deferred shading (advdeferred.hip).  The curvature planes are one float4
+// per pixel, (k1, k2, dir.x, dir.y): the lighting pass reads a neighbour in one 16-B fetch.
+constexpr int kAdvColorMapSize = 256;  // curvatureColorMap: float4 texels (rgb, 1)
+constexpr int kAdvRidgeMapSize = 256;  // ridgeValleyMap: 256 x 256 floats (its .r channel)
+struct AdvShadeArgs {                // lighting_pass.comp's and post_process.frag's uniforms
+  int W, H;
+  float eye[3];                      // viewPos: CameraEye of the kept frame
+  float light[3];                    // lightPos
+  float light_color[3];
+  float alpha;                       // objectColor.a
+  float ka, kd, ks, shininess;
+  float flow_speed, flow_scale, time;
+  int show_ridges, show_valleys;
+  float accessibility;               // accessibilityStrength
+  float screen[2];                   // screenSize, resolved (> 0)
+  float exposure, gamma;
+};
+
 // Several frames in one ray-march launch (cvr_render_rc1pass_frames): frame f
 // takes workgroups [f * grid, (f + 1) * grid) and differs from frame 0 only in
 // its view (camera) and its outputs.  grid is a multiple of 8 whenever the
@@ -616,6 +634,24 @@ struct Ctx {
     size_t bytes = 0;                  // the planes (cvr_device_bytes)
     int launches = 0;
   } deferred;
+  // advanced deferred shading (cvr_advdeferred.cpp): the curvature planes of the kept
+  // G-buffer (16 B per pixel; valid for that G-buffer and the projection scales p00 /
+  // p11: every geometry pass clears `valid`, deferred_drop frees them), the two tables
+  // of the lighting pass (built once; the colour map again when s or v change), the
+  // feature-pixel counter of the last lighting pass, and the curvature launches so far
+  struct AdvDeferred {
+    float4* d_curv = nullptr;
+    float4* d_cmap = nullptr;
+    float* d_ridge = nullptr;
+    unsigned long long* d_features = nullptr;
+    bool valid = false;
+    bool shaded = false;               // a lighting pass has written d_features
+    float p00 = 0, p11 = 0;
+    float cmap_s = 0, cmap_v = 0;      // what d_cmap was built from
+    size_t bytes = 0;                  // the planes (cvr_device_bytes)
+    size_t table_bytes = 0;            // the tables
+    int launches = 0;
+  } adv;
   unsigned long long* d_tile_samples = nullptr;   // per-wave-tile sample counts (zeroed)
   int tile_samples_n = 0;
   // d_tile_samples and d_shade are one set per context: a frame that uses them on
@@ -746,6 +782,14 @@ hipError_t launch_deferred_geometry(const Ctx& c, const IsoArgs& q, const float 
                                     float4* gbuf, unsigned long long* hits, hipStream_t s);
 hipError_t launch_deferred_shade(const DeferredShadeArgs& q, const float4* gbuf, float4* out, int half,
                                  uint32_t* samples, unsigned long long* total, hipStream_t s);
+// advdeferred.hip: the curvature pass over a G-buffer's normal plane (p00, p11: the
+// projection's x and y scales) and the feature-lighting pass with the tone map
+// (features: += pixels whose feature colour has red or green set)
+hipError_t launch_adv_curvature(int W, int H, float p00, float p11, const float4* gbuf, float4* curv,
+                                hipStream_t s);
+hipError_t launch_adv_shade(const AdvShadeArgs& q, const float4* gbuf, const float4* curv, const float4* cmap,
+                            const float* ridge, float4* out, int half, uint32_t* samples,
+                            unsigned long long* total, unsigned long long* features, hipStream_t s);
 // codec.hip: the lossless per-tile code of RGBA16F tiles (cvr_encode_tiles)
 size_t tile_code_bound_bytes(int tile, int ntiles);
 hipError_t launch_tile_encode(const void* d_tiles, int tile, int ntiles, void* d_stream,

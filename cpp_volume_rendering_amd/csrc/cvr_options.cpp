@@ -169,6 +169,20 @@ const Option kOptions[] = {
      },
      1, 0, nullptr, nullptr, nullptr},
     {"deferred_launches", nullptr, [](const Ctx* c) { return c->deferred.launches; }, 1, 0, nullptr, nullptr, nullptr},
+    // the curvature launches so far, and the pixels of the last advanced lighting pass whose
+    // feature colour has red or green set (waits for that pass; -1: none yet)
+    {"advdeferred_curvature_launches", nullptr, [](const Ctx* c) { return c->adv.launches; }, 1, 0, nullptr, nullptr,
+     nullptr},
+    {"advdeferred_ridge_pixels", nullptr,
+     [](const Ctx* c) {
+       unsigned long long n = 0;
+       if (!c->adv.shaded || hipSetDevice(c->device) != hipSuccess ||
+           hipStreamSynchronize(c->stream) != hipSuccess ||
+           hipMemcpy(&n, c->adv.d_features, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
+         return -1;
+       return (int)n;
+     },
+     1, 0, nullptr, nullptr, nullptr},
 };
 
 const Option* find_option(const char* key) {

@@ -25,6 +25,7 @@
 #include "cvr_device.h"
 #include "march_common.h"
 #include "iso_common.h"
+#include "gbuffer_common.h"
 
 namespace cvr {
 
@@ -155,16 +156,6 @@ deferred_geometry_kernel(IsoArgs Q, float4 clear, const uint4* __restrict__ cell
   const unsigned long long v = wave_sum((unsigned long long)(state == 2 ? 1u : 0u));
   if (lane == 0 && v) atomicAdd(hits, v);
 }
-
-// texture(g, vec2(pixel) / vec2(size)) with GL_NEAREST: the texel of a texel edge
-// (CVR-SPEC): clamp(int(floor(fl(fl(p / s) * s))), 0, s - 1)
-__device__ __forceinline__ int edge_texel(int p, int s) {
-  const float u = (float)p / (float)s;
-  const int t = (int)floorf(u * (float)s);
-  return min(max(t, 0), s - 1);
-}
-
-__device__ __forceinline__ float length3(f3 v) { return sqrtf(dot3(v, v)); }
 
 __global__ void __launch_bounds__(256)
 deferred_shade_kernel(DeferredShadeArgs Q, const float4* __restrict__ gbuf, float4* __restrict__ out,

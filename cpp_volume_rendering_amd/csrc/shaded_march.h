@@ -53,9 +53,6 @@ constexpr int kJobSlots = 64 * kJobsPerLane;
 __device__ __forceinline__ f3 vmad(f3 d, float t, f3 p) {
   return f3{fmaf(d.x, t, p.x), fmaf(d.y, t, p.y), fmaf(d.z, t, p.z)};
 }
-__device__ __forceinline__ f3 cross3(f3 x, f3 y) {   // glm / GLSL cross, no fma
-  return f3{x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y};
-}
 
 template <class SH, class = void>
 struct ShaderGate {

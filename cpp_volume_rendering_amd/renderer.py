@@ -1275,6 +1275,105 @@ class DeferredShading(RayCasting1PassIsoAdapt):
     _ENTRY = "cvr_render_deferred"
 
 
+class AdvancedDeferredShading(DeferredShading):
+    """HIP implementation of AdvancedDeferredShading
+    (cppvolrend/structured/AdvancedDeferredShading/AdvancedDeferredShading.cpp):
+    DeferredShading's geometry pass and tone map, with a screen-space curvature pass over the
+    G-buffer's normals and a feature-lighting pass (Blinn-Phong with the shader's own constants,
+    accessibility, a curvature colour map, ridge and valley lines, a flow term) between them.
+    The G-buffer and the curvature planes are kept: a change of lighting or feature parameters
+    runs the lighting pass alone, a change of the camera, the volume or a march parameter all
+    three passes."""
+
+    def __init__(self, device: int = 0):
+        super().__init__(device)
+        self._params = N.AdvDeferredParams()
+        N.lib().cvr_advdeferred_params_default(ctypes.byref(self._params))
+        d = self._params
+        self.gbuffer_clear = tuple(d.gbuffer_clear)     # Redraw (:724)
+        # lighting_pass.comp:200-207: the shader's constants, not the rendering parameters'
+        self.ka, self.kd, self.ks, self.shininess = d.ka, d.kd, d.ks, d.shininess
+        self.m_flow_speed = d.flow_speed                # AdvancedDeferredShading.h:129-133
+        self.m_flow_scale = d.flow_scale
+        self.m_show_ridges = bool(d.show_ridges)
+        self.m_show_valleys = bool(d.show_valleys)
+        self.m_accessibility_strength = d.accessibility_strength
+        self.m_current_time = d.time                    # constructor (:130)
+        self.s, self.v = d.colormap_s, d.colormap_v     # Init (:536-537)
+        self.screen_size = tuple(d.screen_size)
+
+    def GetName(self): return "Advanced Deferred Rendering"
+
+    @property
+    def curvature_launches(self) -> int:
+        return int(N.lib().cvr_get_option(self.device.handle, b"advdeferred_curvature_launches"))
+
+    @property
+    def ridge_pixels(self) -> int:
+        """Pixels of the last lighting pass with a ridge or valley colour (waits for it)."""
+        return int(N.lib().cvr_get_option(self.device.handle, b"advdeferred_ridge_pixels"))
+
+    def curvature_planes(self):
+        """k1, k2 (H, W) and the projected direction of k1 (H, W, 2) of the kept frame."""
+        W, H = self._frame.width, self._frame.height
+        k1, k2, d = (np.zeros(s, np.float32) for s in ((H, W), (H, W), (H, W, 2)))
+        h = self.device.handle
+        N.check(N.lib().cvr_advdeferred_read_curvature(h, W, H, N.fptr(k1), N.fptr(k2), N.fptr(d)),
+                "cvr_advdeferred_read_curvature", h)
+        return k1, k2, d
+
+    def Update(self, camera: Camera) -> bool:
+        rp = self.m_ext_rendering_parameters or RenderingParameters()
+        self._frame = self._camera_frame(camera)
+        p = self._params
+        p.num_blocks[:] = [int(b) for b in self.num_blocks]
+        p.isovalue = float(self.m_u_isovalue)
+        p.step_small = float(self.m_u_step_size_small)
+        p.step_large = float(self.m_u_step_size_large)
+        p.step_range = float(self.m_u_step_size_range)
+        p.gbuffer_clear[:] = [float(c) for c in self.gbuffer_clear]
+        p.color[:] = [float(c) for c in self.m_u_color]
+        p.ka, p.kd, p.ks, p.shininess = self.ka, self.kd, self.ks, self.shininess
+        p.light_color[:] = [float(v) for v in self.light_color]
+        p.light_pos[:] = [float(v) for v in rp.light_position]    # LightingPass (:372)
+        p.exposure, p.gamma = float(self.exposure), float(self.gamma)
+        p.flow_speed, p.flow_scale = float(self.m_flow_speed), float(self.m_flow_scale)
+        p.time = float(self.m_current_time)
+        p.show_ridges, p.show_valleys = int(self.m_show_ridges), int(self.m_show_valleys)
+        p.accessibility_strength = float(self.m_accessibility_strength)
+        p.screen_size[:] = [float(v) for v in self.screen_size]
+        p.colormap_s, p.colormap_v = float(self.s), float(self.v)
+        key = (bytes(self._frame), tuple(p.num_blocks), p.isovalue, p.step_small, p.step_large, p.step_range,
+               tuple(p.gbuffer_clear), id(self._dev))
+        self._geometry_outdated = key != self._geometry_key
+        self._pending_key = key
+        return True
+
+    def render_to(self, frame: N.Frame, out: N.Output):
+        h = self.device.handle
+        if frame is self._frame and not self._geometry_outdated:
+            N.check(N.lib().cvr_advdeferred_shade(h, frame.width, frame.height, ctypes.byref(self._params),
+                                                  ctypes.byref(out)), "cvr_advdeferred_shade", h)
+            return
+        self._geometry_key = None
+        N.check(N.lib().cvr_render_advdeferred(h, ctypes.byref(frame), ctypes.byref(self._params),
+                                               ctypes.byref(out)), "cvr_render_advdeferred", h)
+        if frame is self._frame:
+            self._geometry_key = self._pending_key
+            self._geometry_outdated = False
+
+    def render_frames_to(self, frames, outs):
+        raise NotImplementedError("AdvancedDeferredShading: one frame per call")
+
+    def FillParameterSpace(self, pspace: dict):
+        pspace.clear()                              # AdvancedDeferredShading.cpp:759-765
+        pspace["StepSizeSmall"] = (0.01, 0.25, 0.05)
+        pspace["StepSizeLarge"] = (0.25, 2.0, 0.25)
+        pspace["StepSizeRange"] = (0.05, 0.26, 0.05)
+
+    _ENTRY = "cvr_render_advdeferred"
+
+
 def composite_over_white(rgba: np.ndarray) -> np.ndarray:
     """Screen image as RenderFrameToScreen::Draw blends it over the white clear colour
     with SRC_ALPHA / ONE_MINUS_SRC_ALPHA (renderingmanager.cpp:103-112), as RGB8."""

@@ -849,6 +849,78 @@ cvr_status  cvr_deferred_shade(cvr_ctx* ctx, int width, int height, const cvr_de
 cvr_status  cvr_deferred_read_gbuffer(cvr_ctx* ctx, int width, int height, float* out_position,
                                       float* out_normal);
 
+/* ----------------------------------------------------------------------------
+ * AdvancedDeferredShading ("Advanced Deferred Rendering", abbreviation "iso";
+ * cppvolrend/structured/AdvancedDeferredShading): DeferredShading's geometry pass and
+ * tone map, with a screen-space curvature pass over the G-buffer's normals
+ * (curvature_pass.comp: principal curvatures k1, k2 and the projected direction of k1)
+ * and a feature-lighting pass (lighting_pass.comp: Blinn-Phong, accessibility shading,
+ * a curvature colour map, ridge and valley lines, a curvature "flow" term) between
+ * them.  The G-buffer is the context's own (cvr_deferred_geometry fills the same one);
+ * the curvature planes are kept next to it, valid for one G-buffer and one pair of
+ * projection scales: any geometry pass invalidates them.
+ *
+ * Where the reference leaves the result undefined: texel lookups are
+ * floor(fl(u * size)) wrapped modulo size (GL_NEAREST, GL_REPEAT), texel 0 for a
+ * coordinate that is not finite; the curvature direction's angle is never formed (cos
+ * and sin are the normalised (k1 - A00, A01), (1, 0) for a zero vector); screenSize and
+ * time, which the application never sets, are parameters.  A negative discriminant
+ * gives NaN curvatures, which are stored and compare false everywhere.
+ *
+ * Whole frames only, like cvr_render_deferred.  Device memory, counted by
+ * cvr_device_bytes: 16 B per pixel for the curvature planes (from the first curvature
+ * pass to the next volume or viewport) and 260 KiB for the two tables (from the first
+ * lighting pass to the context's end).  Read-only options:
+ * "advdeferred_curvature_launches" (curvature launches so far) and
+ * "advdeferred_ridge_pixels" (pixels of the last lighting pass whose feature colour has
+ * red or green set, after show_ridges / show_valleys; reading it waits for that pass;
+ * -1 before the first).
+ * -------------------------------------------------------------------------- */
+typedef struct cvr_advdeferred_params {
+  float isovalue;              /* the march and tone-map fields of cvr_deferred_params     */
+  float step_small;
+  float step_large;
+  float step_range;
+  int   num_blocks[3];         /* (4, 4, 4), AdvancedDeferredShading.cpp:561               */
+  float color[4];              /* m_u_color: only its alpha reaches the frame (>= 0)       */
+  float ka, kd, ks, shininess; /* lighting_pass.comp:200-207's constants 0.1 0.7 0.2 32    */
+  float light_color[3];        /* lightColor (1, 1, 1), AdvancedDeferredShading.cpp:380    */
+  float light_pos[3];          /* lightPos (light 0 of the reference's list)               */
+  float exposure;              /* 1.0 (Redraw :752); <= 0: no exposure map                 */
+  float gamma;                 /* 2.2 (Redraw :753); <= 0: no gamma map                    */
+  float gbuffer_clear[4];      /* Redraw's glClearColor (1, 1, 1, 1), :724                 */
+  float flow_speed;            /* m_flow_speed 1 (AdvancedDeferredShading.h:129)           */
+  float flow_scale;            /* m_flow_scale 10 (:130)                                   */
+  float time;                  /* m_current_time 0 (constructor :130; never advanced)      */
+  int   show_ridges;           /* m_show_ridges true (:131)                                */
+  int   show_valleys;          /* m_show_valleys true (:132)                               */
+  float accessibility_strength;/* m_accessibility_strength 0.5 (:133)                      */
+  float screen_size[2];        /* screenSize, never set by the application (:379 is a
+                                  comment): (0, 0); a component <= 0 is the frame's width
+                                  or height                                                */
+  float colormap_s;            /* s 0.6 (Init :536): the colour map's saturation           */
+  float colormap_v;            /* v 0.2 (Init :537): its value                             */
+} cvr_advdeferred_params;
+void        cvr_advdeferred_params_default(cvr_advdeferred_params* out);
+/* One frame: geometry, curvature and lighting pass on the context stream, no host
+ * synchronisation between them.  samples and total are the geometry pass's counts.
+ * Errors as cvr_render_deferred; also CVR_ERR_ARG for a NaN feature parameter. */
+cvr_status  cvr_render_advdeferred(cvr_ctx* ctx, const cvr_frame* frame, const cvr_advdeferred_params* params,
+                                   const cvr_output* out);
+/* The curvature pass alone over the kept G-buffer, for `frame`'s projection (only its
+ * size, fovy_deg and aspect are read; `params` is checked, nothing of it is read).
+ * CVR_ERR_STATE without a G-buffer of that size. */
+cvr_status  cvr_advdeferred_curvature(cvr_ctx* ctx, const cvr_frame* frame, const cvr_advdeferred_params* params);
+/* The lighting pass alone over the kept G-buffer and curvature planes (the relight
+ * path): the lighting, feature, colour-map and tone-map fields of `params` are read.
+ * CVR_ERR_STATE without valid curvature planes, CVR_ERR_ARG for another viewport. */
+cvr_status  cvr_advdeferred_shade(cvr_ctx* ctx, int width, int height, const cvr_advdeferred_params* params,
+                                  const cvr_output* out);
+/* The kept curvature planes: k1 and k2 (width x height floats each) and the direction
+ * (width x height x 2); blocks.  CVR_ERR_STATE without valid planes. */
+cvr_status  cvr_advdeferred_read_curvature(cvr_ctx* ctx, int width, int height, float* out_k1, float* out_k2,
+                                           float* out_dir);
+
 /* The reference renderers' default parameters for `variant`. */
 void        cvr_iso_params_default(int variant, cvr_iso_params* out);
 /* One isosurface frame (first hits composited front to back with Color).  The

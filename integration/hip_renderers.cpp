@@ -628,3 +628,94 @@ void HipDeferredShading::FillParameterSpace (ParameterSpace& pspace)
   pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeLarge", &m_u_step_size_large, 0.25f, 2.0f, 0.25f));
   pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeRange", &m_u_step_size_range, 0.05f, 0.26f, 0.05f));
 }
+
+////////////////////////////////////////////////////////////////////////////////
+// AdvancedDeferredShading (AdvancedDeferredShading.cpp:119-135, 532-765)
+////////////////////////////////////////////////////////////////////////////////
+HipAdvancedDeferredShading::HipAdvancedDeferredShading ()
+  : m_u_isovalue(0.5f)                 // AdvancedDeferredShading.cpp:124-130
+  , m_u_step_size_small(0.05f)
+  , m_u_step_size_large(1.0f)
+  , m_u_step_size_range(0.1f)
+  , m_u_color(0.66f, 0.6f, 0.05f, 1.0f)
+  , m_current_time(0.0f)
+  , m_flow_speed(1.0f)                 // AdvancedDeferredShading.h:129-133
+  , m_flow_scale(10.0f)
+  , m_show_ridges(true)
+  , m_show_valleys(true)
+  , m_accessibility_strength(0.5f)
+  , s(0.6f)                            // Init (:536-537)
+  , v(0.2f)
+  , m_params()
+  , m_kept_frame()
+  , m_kept_params()
+  , m_geometry_kept(false)
+{
+  cvr_advdeferred_params_default(&m_params);
+}
+
+bool HipAdvancedDeferredShading::Init (int swidth, int sheight)
+{
+  if (IsBuilt()) Clean();
+  if (m_ext_data_manager->GetCurrentVolumeTexture() == nullptr) return false;
+  if (!UploadVolume()) return false;
+  m_geometry_kept = false;
+  Reshape(swidth, sheight);
+  SetBuilt(true);
+  SetOutdated();
+  return true;
+}
+
+// UpdateGeometryPassUniforms (:661-689) and LightingPass's uniforms (:371-380).  Ka, Kd, Ks
+// and the shininess are constants of lighting_pass.comp: the library's defaults stay.
+bool HipAdvancedDeferredShading::Update (vis::Camera* camera)
+{
+  vis::RenderingParameters* rp = m_ext_rendering_parameters;
+  FillFrame(camera);
+  m_params.isovalue = m_u_isovalue;
+  m_params.step_small = m_u_step_size_small;
+  m_params.step_large = m_u_step_size_large;
+  m_params.step_range = m_u_step_size_range;
+  for (int i = 0; i < 4; i++) m_params.color[i] = m_u_color[i];
+  copy3(m_params.light_pos, rp->GetBlinnPhongLightingPosition());
+  m_params.time = m_current_time;
+  m_params.flow_speed = m_flow_speed;
+  m_params.flow_scale = m_flow_scale;
+  m_params.show_ridges = m_show_ridges ? 1 : 0;
+  m_params.show_valleys = m_show_valleys ? 1 : 0;
+  m_params.accessibility_strength = m_accessibility_strength;
+  m_params.colormap_s = s;
+  m_params.colormap_v = v;
+  return true;
+}
+
+static bool same_geometry (const cvr_advdeferred_params& a, const cvr_advdeferred_params& b)
+{
+  return a.isovalue == b.isovalue && a.step_small == b.step_small && a.step_large == b.step_large &&
+         a.step_range == b.step_range && !std::memcmp(a.num_blocks, b.num_blocks, sizeof(a.num_blocks)) &&
+         !std::memcmp(a.gbuffer_clear, b.gbuffer_clear, sizeof(a.gbuffer_clear));
+}
+
+cvr_status HipAdvancedDeferredShading::RenderFrame (const cvr_output* out)
+{
+  if (m_geometry_kept && !std::memcmp(&frame_, &m_kept_frame, sizeof(cvr_frame)) &&
+      same_geometry(m_params, m_kept_params))
+    return cvr_advdeferred_shade(m_cvr, frame_.width, frame_.height, &m_params, out);
+  m_geometry_kept = false;
+  const cvr_status st = cvr_render_advdeferred(m_cvr, &frame_, &m_params, out);
+  if (st == CVR_OK) {
+    m_kept_frame = frame_;
+    m_kept_params = m_params;
+    m_geometry_kept = true;
+  }
+  return st;
+}
+
+// AdvancedDeferredShading.cpp:759-765
+void HipAdvancedDeferredShading::FillParameterSpace (ParameterSpace& pspace)
+{
+  pspace.ClearParameterDimensions();
+  pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeSmall", &m_u_step_size_small, 0.01f, 0.25f, 0.05f));
+  pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeLarge", &m_u_step_size_large, 0.25f, 2.0f, 0.25f));
+  pspace.AddParameterDimension(new ParameterRangeFloat("StepSizeRange", &m_u_step_size_range, 0.05f, 0.26f, 0.05f));
+}

@@ -13,6 +13,7 @@
  *   HipSBTMDirectionalOcclusionShading <- SBTMDirectionalOcclusionShading
  *                                                              (sbtmdos/sbtmdosrenderer.h)
  *   HipDeferredShading                 <- DeferredShading      (DeferredShading/DeferredShading.h)
+ *   HipAdvancedDeferredShading         <- AdvancedDeferredShading (AdvancedDeferredShading/AdvancedDeferredShading.h)
  *   HipRayCasting1PassIsoAdapt       <- RayCasting1PassIsoAdapt (rc1pisoadapt/rc1pisoadaptrenderer.h)
  *   HipCustomRayCasting1PassIsoAdapt <- CustomRayCasting1PassIsoAdapt (rc1pisocustom/...)
  *   HipCustomRayCasting1PassIsodfsAdapt <- CustomRayCasting1PassIsodfsAdapt (rc1pisodfscustom/...)
@@ -286,6 +287,43 @@ protected:
   cvr_deferred_params m_params;
   cvr_frame m_kept_frame;              // what the kept G-buffer was marched from
   cvr_deferred_params m_kept_params;
+  bool m_geometry_kept;
+};
+
+// AdvancedDeferredShading (AdvancedDeferredShading/AdvancedDeferredShading.cpp): the same
+// march, a curvature pass over the kept G-buffer and the feature-lighting pass with the tone
+// map (cvr_render_advdeferred).  Update marches again only when the frame or a march
+// parameter changed; otherwise Redraw runs the lighting pass over the kept planes
+// (cvr_advdeferred_shade).  Whole frames only.
+class HipAdvancedDeferredShading : public HipRendererBase
+{
+public:
+  HipAdvancedDeferredShading ();
+  const char* GetName () override { return "Advanced Deferred Rendering (HIP, MI355X)"; }
+  const char* GetAbbreviationName () override { return "iso_hip"; }
+  bool Init (int shader_width, int shader_height) override;
+  bool Update (vis::Camera* camera) override;
+  void FillParameterSpace (ParameterSpace& pspace) override;
+
+  // AdvancedDeferredShading.cpp:124-130, AdvancedDeferredShading.h:129-133, Init :536-537
+  float m_u_isovalue;
+  float m_u_step_size_small;
+  float m_u_step_size_large;
+  float m_u_step_size_range;
+  glm::vec4 m_u_color;
+  float m_current_time;
+  float m_flow_speed;
+  float m_flow_scale;
+  bool m_show_ridges;
+  bool m_show_valleys;
+  float m_accessibility_strength;
+  float s, v;
+
+protected:
+  cvr_status RenderFrame (const cvr_output* out) override;
+  cvr_advdeferred_params m_params;
+  cvr_frame m_kept_frame;              // what the kept planes were computed from
+  cvr_advdeferred_params m_kept_params;
   bool m_geometry_kept;
 };
 

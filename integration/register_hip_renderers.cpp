@@ -22,6 +22,7 @@ void RegisterHipRenderers ()
   RenderingManager::Instance()->AddVolumeRenderer(new HipVoxelConeTracingSGPU());
   RenderingManager::Instance()->AddVolumeRenderer(new HipSBTMDirectionalOcclusionShading());
   RenderingManager::Instance()->AddVolumeRenderer(new HipDeferredShading());
+  RenderingManager::Instance()->AddVolumeRenderer(new HipAdvancedDeferredShading());
   RenderingManager::Instance()->AddVolumeRenderer(new HipRayCasting1PassIsoAdapt());
   RenderingManager::Instance()->AddVolumeRenderer(new HipCustomRayCasting1PassIsoAdapt());
   RenderingManager::Instance()->AddVolumeRenderer(new HipCustomRayCasting1PassIsodfsAdapt());

@@ -8,6 +8,11 @@ the relight-only frame), and cvr_render_deferred (both, as one frame).  A second
 resolution, ungated, reports cvr_render_iso variant 0 on the same scene and camera, as the
 nearest existing renderer.
 
+With --advanced, a further line per resolution reports the advanced deferred renderer on the
+same scene and camera: cvr_deferred_geometry (its geometry pass is that one),
+cvr_advdeferred_curvature, cvr_advdeferred_shade (the feature-lighting pass and tone map: the
+relight-only frame) and cvr_render_advdeferred (all three as one frame).
+
 Times are HIP events around the call, medians over --steps frames after --warmup untimed
 ones, in milliseconds, with the spread (min, max).  Prints one JSON line per renderer (also
 appended to --out when given).  A measurement: no target.
@@ -26,8 +31,9 @@ import torch  # noqa: E402
 
 from cpp_volume_rendering_amd import _native as N  # noqa: E402
 from cpp_volume_rendering_amd import datasets as D  # noqa: E402
-from cpp_volume_rendering_amd.renderer import (Camera, CustomRayCasting1PassIsoAdapt,  # noqa: E402
-                                               DataManager, DeferredShading, RenderingParameters)
+from cpp_volume_rendering_amd.renderer import (AdvancedDeferredShading, Camera,  # noqa: E402
+                                               CustomRayCasting1PassIsoAdapt, DataManager, DeferredShading,
+                                               RenderingParameters)
 
 
 def timed(call, steps, warmup):
@@ -43,12 +49,52 @@ def timed(call, steps, warmup):
     return dict(median=statistics.median(ms), min=min(ms), max=max(ms), n=len(ms))
 
 
+def advanced(a, dm, rp, cam, W, base):
+    """The advanced deferred renderer's pass times at W x W: one JSON line."""
+    L = N.lib()
+    r = AdvancedDeferredShading(0)
+    r.SetExternalResources(dm, rp)
+    assert r.Init(W, W)
+    r.Update(cam)
+    h = r.device.handle
+    r.device.set_stream(torch.cuda.current_stream(0).cuda_stream)
+    out = N.Output(r.rgba.data_ptr(), None, None, 1, N.FORMAT_RGBA32F)
+    frame, p = r._frame, r._params
+    g = N.DeferredParams()
+    L.cvr_deferred_params_default(ctypes.byref(g))
+    g.isovalue, g.step_small, g.step_large, g.step_range = p.isovalue, p.step_small, p.step_large, p.step_range
+    g.num_blocks[:] = list(p.num_blocks)
+    g.gbuffer_clear[:] = list(p.gbuffer_clear)
+
+    def geometry():
+        N.check(L.cvr_deferred_geometry(h, ctypes.byref(frame), ctypes.byref(g)), "cvr_deferred_geometry", h)
+
+    def curvature():
+        N.check(L.cvr_advdeferred_curvature(h, ctypes.byref(frame), ctypes.byref(p)), "cvr_advdeferred_curvature", h)
+
+    def shade():
+        N.check(L.cvr_advdeferred_shade(h, W, W, ctypes.byref(p), ctypes.byref(out)), "cvr_advdeferred_shade", h)
+
+    def whole():
+        N.check(L.cvr_render_advdeferred(h, ctypes.byref(frame), ctypes.byref(p), ctypes.byref(out)),
+                "cvr_render_advdeferred", h)
+
+    line = dict(base, renderer="cvr_render_advdeferred", geometry_ms=timed(geometry, a.steps, a.warmup),
+                curvature_ms=timed(curvature, a.steps, a.warmup), shade_ms=timed(shade, a.steps, a.warmup),
+                frame_ms=timed(whole, a.steps, a.warmup), relight_ms=timed(shade, a.steps, a.warmup),
+                hits=L.cvr_get_option(h, b"deferred_hits"),
+                ridge_pixels=L.cvr_get_option(h, b"advdeferred_ridge_pixels"))
+    r.Clean()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--size", type=int, default=512, help="volume N^3")
     ap.add_argument("--res", type=int, nargs="+", default=[2048, 1024], help="frame W = H")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--advanced", action="store_true", help="also time the advanced deferred renderer's passes")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
 
@@ -89,6 +135,9 @@ def main():
                           hits=L.cvr_get_option(h, b"deferred_hits")))
         print(json.dumps(lines[-1]), flush=True)
         r.Clean()
+        if a.advanced:
+            lines.append(advanced(a, dm, rp, cam, W, base))
+            print(json.dumps(lines[-1]), flush=True)
         i = CustomRayCasting1PassIsoAdapt(0)
         i.SetExternalResources(dm, rp)
         assert i.Init(W, W)
