@@ -170,25 +170,19 @@ adv_shade_kernel(AdvShadeArgs Q, const float4* __restrict__ gbuf, const float4* 
   const int W = Q.W, H = Q.H;
   const long long npix = (long long)W * H;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool inside = i < npix;
   uint32_t count = 0, featured = 0;
-  if (i < npix) {
-    const int py = (int)(i / W), px = (int)(i - (long long)py * W);
-    const long long g = (long long)edge_texel(py, H) * W + edge_texel(px, W);
-    const float4 gp = gbuf[g], gn = gbuf[npix + g];
-    count = __float_as_uint(gbuf[npix + i].w);
-    const f3 pos = xyz(gp), raw = xyz(gn);
-    float4 c;
-    if (length3(raw) < 0.1f) {   // background (:189)
+  float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (inside) {
+    const GBufferPixel g = gbuffer_fetch(gbuf, W, H, npix, i);
+    count = g.count;
+    if (length3(g.raw) < 0.1f) {   // background (:189)
       c = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     } else {
-      const float u = (float)px / (float)W, v = (float)py / (float)H;   // texCoord (:182)
-      const f3 n = normalize3(raw);
-      const f3 L = normalize3(f3{Q.light[0] - pos.x, Q.light[1] - pos.y, Q.light[2] - pos.z});
-      const f3 V = normalize3(f3{Q.eye[0] - pos.x, Q.eye[1] - pos.y, Q.eye[2] - pos.z});
-      const f3 Hd = normalize3(f3{L.x + V.x, L.y + V.y, L.z + V.z});
-      const float diff = fmaxf(dot3(n, L), 0.0f);
-      const float spec = cvr_powf(fmaxf(dot3(n, Hd), 0.0f), Q.shininess);
-      const float4 cv = curv[g];
+      const float u = (float)g.px / (float)W, v = (float)g.py / (float)H;   // texCoord (:182)
+      const f3 n = normalize3(g.raw);
+      const PhongTerms ph = gbuffer_phong(Q.light, Q.eye, g.pos, n, Q.shininess);
+      const float4 cv = curv[g.texel];
       const float k1 = cv.x, k2 = cv.y;
       const f2 dir{cv.z, cv.w};
       // computeMeanCurvature and the colour map (:217-218)
@@ -199,7 +193,7 @@ adv_shade_kernel(AdvShadeArgs Q, const float4* __restrict__ gbuf, const float4* 
       const float4 c0 = cmap[m0], c1 = cmap[m1];
       const float curvature[3] = {lerpf(c0.x, c1.x, ma), lerpf(c0.y, c1.y, ma), lerpf(c0.z, c1.z, ma)};
       // computeAccessibility (:88-100)
-      const float ndotv = fmaxf(dot3(n, V), 0.0f);
+      const float ndotv = fmaxf(dot3(n, ph.V), 0.0f);
       const float access = clamp01(1.0f - Q.accessibility * (clamp01((-mean) * 2.0f) + (1.0f - ndotv)));
       // computeRidgeValley (:102-159)
       float fr = 0.0f, fg = 0.0f, fa = 0.0f;
@@ -235,8 +229,8 @@ adv_shade_kernel(AdvShadeArgs Q, const float4* __restrict__ gbuf, const float4* 
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         const float ambient = Q.ka * Q.light_color[k];
-        const float diffuse = (Q.kd * diff) * Q.light_color[k];
-        const float specular = (Q.ks * spec) * Q.light_color[k];
+        const float diffuse = (Q.kd * ph.diff) * Q.light_color[k];
+        const float specular = (Q.ks * ph.spec) * Q.light_color[k];
         float f = (ambient + diffuse) + specular;
         f = f * access;
         f = mixf(f, curvature[k], 0.3f);
@@ -245,25 +239,9 @@ adv_shade_kernel(AdvShadeArgs Q, const float4* __restrict__ gbuf, const float4* 
       }
       c = make_float4(rgb[0], rgb[1], rgb[2], Q.alpha);
     }
-    // post_process.frag: the quad samples finalImage at the pixel's centre, the texel itself
-    if (Q.exposure > 0.0f) {
-      c.x = 1.0f - cvr_expf((-c.x) * Q.exposure);
-      c.y = 1.0f - cvr_expf((-c.y) * Q.exposure);
-      c.z = 1.0f - cvr_expf((-c.z) * Q.exposure);
-    }
-    if (Q.gamma > 0.0f) {
-      const float e = 1.0f / Q.gamma;
-      c.x = cvr_powf(c.x, e);
-      c.y = cvr_powf(c.y, e);
-      c.z = cvr_powf(c.z, e);
-    }
-    store_rgba(out, i, c, half);
-    if (samples) samples[i] = count;
+    tone_map(c, Q.exposure, Q.gamma);
   }
-  if (total) {
-    const unsigned long long t = wave_sum((unsigned long long)count);
-    if ((threadIdx.x & 63) == 0 && t) atomicAdd(total, t);
-  }
+  gbuffer_pixel_tail(inside, out, i, c, half, samples, count, total);
   const unsigned long long f = wave_sum((unsigned long long)featured);
   if ((threadIdx.x & 63) == 0 && f) atomicAdd(features, f);
 }
@@ -274,8 +252,7 @@ hipError_t launch_adv_curvature(int W, int H, float p00, float p11, const float4
                                 hipStream_t s) {
   const long long npix = (long long)W * H;
   if (npix <= 0) return hipSuccess;
-  hipLaunchKernelGGL(adv_curvature_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, W, H, p00, p11,
-                     gbuf, curv);
+  hipLaunchKernelGGL(adv_curvature_kernel, pixel_grid(npix), dim3(kPixelBlock), 0, s, W, H, p00, p11, gbuf, curv);
   return hipGetLastError();
 }
 
@@ -284,8 +261,8 @@ hipError_t launch_adv_shade(const AdvShadeArgs& q, const float4* gbuf, const flo
                             unsigned long long* total, unsigned long long* features, hipStream_t s) {
   const long long npix = (long long)q.W * q.H;
   if (npix <= 0) return hipSuccess;
-  hipLaunchKernelGGL(adv_shade_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, q, gbuf, curv, cmap,
-                     ridge, out, half, samples, total, features);
+  hipLaunchKernelGGL(adv_shade_kernel, pixel_grid(npix), dim3(kPixelBlock), 0, s, q, gbuf, curv, cmap, ridge, out,
+                     half, samples, total, features);
   return hipGetLastError();
 }
 

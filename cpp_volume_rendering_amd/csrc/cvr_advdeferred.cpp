@@ -1,10 +1,14 @@
 // cvr_advdeferred.cpp — advanced deferred isosurface shading (AdvancedDeferredShading;
 // advdeferred.hip): the argument checks, the curvature planes kept next to the context's
 // G-buffer, the lighting pass's two tables, and the three passes of a frame.  The
-// geometry pass and the G-buffer are cvr_deferred.cpp's.
+// geometry pass, the G-buffer and everything the parameters and the lighting pass have
+// in common with DeferredShading's are cvr_deferred.cpp's and cvr_host.h's: this file
+// keeps the feature parameters, the curvature pass and the tables.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
+#include <cstring>
 #include <vector>
 
 #include "cvr_host.h"
@@ -31,32 +35,24 @@ void advdeferred_drop(Ctx* c, bool destroy) {
 
 namespace {
 
-// The march fields, as the geometry pass takes them.
-cvr_deferred_params march_params(const cvr_advdeferred_params* p) {
-  cvr_deferred_params d{};
-  d.isovalue = p->isovalue;
-  d.step_small = p->step_small;
-  d.step_large = p->step_large;
-  d.step_range = p->step_range;
-  for (int i = 0; i < 3; i++) d.num_blocks[i] = p->num_blocks[i];
-  for (int i = 0; i < 4; i++) d.gbuffer_clear[i] = p->gbuffer_clear[i];
+// The parameters' common part: cvr_advdeferred_params begins with cvr_deferred_params'
+// fields, in its order (include/cvr.h), so the geometry pass, the lighting checks and
+// the shade arguments' filler take that prefix, and a field added to both is in it.
+static_assert(offsetof(cvr_advdeferred_params, flow_speed) == sizeof(cvr_deferred_params) &&
+                  offsetof(cvr_advdeferred_params, gbuffer_clear) == offsetof(cvr_deferred_params, gbuffer_clear),
+              "cvr_advdeferred_params must begin with cvr_deferred_params' fields");
+cvr_deferred_params deferred_prefix(const cvr_advdeferred_params* p) {
+  cvr_deferred_params d;
+  std::memcpy(&d, p, sizeof(d));
   return d;
 }
 
-// What the lighting pass reads of the parameters (cvr_powf is specified for x >= 0).
+// What the lighting pass reads of the parameters: the common checks, and its own scalars'
 cvr_status check_shade_params(Ctx* c, const char* who, const cvr_advdeferred_params* p) {
-  const float scalars[] = {p->ka,         p->kd,         p->ks,   p->shininess,
-                           p->exposure,   p->gamma,      p->flow_speed,
-                           p->flow_scale, p->time,       p->accessibility_strength,
+  const float scalars[] = {p->flow_speed, p->flow_scale, p->time,           p->accessibility_strength,
                            p->colormap_s, p->colormap_v, p->screen_size[0], p->screen_size[1]};
-  if (any_nan(scalars, (int)(sizeof(scalars) / sizeof(scalars[0]))) || any_nan(p->color, 4) ||
-      any_nan(p->light_color, 3) || any_nan(p->light_pos, 3))
-    return fail(c, CVR_ERR_ARG, "%s: a lighting, feature or tone-map parameter is NaN", who);
-  if (p->ka < 0.0f || p->kd < 0.0f || p->ks < 0.0f)
-    return fail(c, CVR_ERR_ARG, "%s: ka, kd and ks must be >= 0", who);
-  if (any_negative(p->color, 4) || any_negative(p->light_color, 3))
-    return fail(c, CVR_ERR_ARG, "%s: the colour and the light colour must be >= 0", who);
-  return CVR_OK;
+  const cvr_deferred_params d = deferred_prefix(p);
+  return deferred_check_lighting(c, who, &d, "lighting, feature or tone-map", any_nan(scalars, 8));
 }
 
 // Result[0][0] and Result[1][1] of Camera::Projection (camera.cpp:286-293): it hands
@@ -143,8 +139,7 @@ cvr_status curvature_pass(Ctx* c, const char* who, const cvr_frame* f) {
   HIP_TRY(c, hipSetDevice(c->device));
   if (!A.d_curv) {   // deferred_drop frees the planes with a G-buffer of another size
     hipError_t e = hipMalloc((void**)&A.d_curv, npix * 16);
-    if (e != hipSuccess)
-      return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(c, who, e);
     A.bytes = npix * 16;
   }
   float p00, p11;
@@ -162,19 +157,10 @@ cvr_status curvature_pass(Ctx* c, const char* who, const cvr_frame* f) {
 cvr_status shade_pass(Ctx* c, const cvr_advdeferred_params* p, const cvr_output* o) {
   const Ctx::Deferred& D = c->deferred;
   Ctx::AdvDeferred& A = c->adv;
+  const cvr_deferred_params d = deferred_prefix(p);
   AdvShadeArgs S{};
-  S.W = D.W;
-  S.H = D.H;
-  for (int i = 0; i < 3; i++) {
-    S.eye[i] = D.eye[i];
-    S.light[i] = p->light_pos[i];
-    S.light_color[i] = p->light_color[i];
-  }
+  fill_shade_lighting(S, D, &d);
   S.alpha = p->color[3];
-  S.ka = p->ka;
-  S.kd = p->kd;
-  S.ks = p->ks;
-  S.shininess = p->shininess;
   S.flow_speed = p->flow_speed;
   S.flow_scale = p->flow_scale;
   S.time = p->time;
@@ -183,31 +169,21 @@ cvr_status shade_pass(Ctx* c, const cvr_advdeferred_params* p, const cvr_output*
   S.accessibility = p->accessibility_strength;
   S.screen[0] = p->screen_size[0] > 0.0f ? p->screen_size[0] : (float)D.W;
   S.screen[1] = p->screen_size[1] > 0.0f ? p->screen_size[1] : (float)D.H;
-  S.exposure = p->exposure;
-  S.gamma = p->gamma;
-  const size_t npix = (size_t)D.W * D.H;
   HIP_TRY(c, hipSetDevice(c->device));
-  cvr_status st = ensure_tables(c, p);
+  const cvr_status st = ensure_tables(c, p);
   if (st != CVR_OK) return st;
-  hipStream_t s = c->stream;
-  FrameOut fo;
-  st = bind_frame_output(c, o, npix, fo);
-  if (st == CVR_OK) st = frame_counters_begin(c, o, 1, s, fo);
-  if (st != CVR_OK) return st;
-  HIP_TRY(c, hipMemsetAsync(A.d_features, 0, sizeof(unsigned long long), s));
-  st = timed_launch(c, s, [&] {
-    return launch_adv_shade(S, D.d_gbuf, A.d_curv, A.d_cmap, A.d_ridge, fo.d_out, fo.half, fo.d_samples, fo.d_total,
-                            A.d_features, s);
-  });
-  if (st != CVR_OK) return st;
-  A.shaded = true;
-  return frame_output_finish(c, o, fo, s);
-}
-
-cvr_status check_viewport(Ctx* c, const char* who, int width, int height) {
-  if (width != c->deferred.W || height != c->deferred.H)
-    return fail(c, CVR_ERR_ARG, "%s: the G-buffer is %dx%d", who, c->deferred.W, c->deferred.H);
-  return CVR_OK;
+  return shade_frame(
+      c, o,
+      [&](hipStream_t s) {
+        HIP_TRY(c, hipMemsetAsync(A.d_features, 0, sizeof(unsigned long long), s));
+        return CVR_OK;
+      },
+      [&](const FrameOut& fo, hipStream_t s) {
+        const hipError_t e = launch_adv_shade(S, D.d_gbuf, A.d_curv, A.d_cmap, A.d_ridge, fo.d_out, fo.half,
+                                              fo.d_samples, fo.d_total, A.d_features, s);
+        if (e == hipSuccess) A.shaded = true;
+        return e;
+      });
 }
 
 }  // namespace
@@ -217,21 +193,12 @@ extern "C" {
 
 void cvr_advdeferred_params_default(cvr_advdeferred_params* p) {
   if (!p) return;
+  cvr_deferred_params d{};
+  deferred_common_defaults(&d);
   *p = cvr_advdeferred_params{};
-  p->isovalue = 0.5f;                            // constructor (AdvancedDeferredShading.cpp:124-128)
-  p->step_small = 0.05f;
-  p->step_large = 1.0f;
-  p->step_range = 0.1f;
-  for (int i = 0; i < 3; i++) p->num_blocks[i] = 4;   // Init (:561)
-  p->color[0] = 0.66f; p->color[1] = 0.6f; p->color[2] = 0.05f; p->color[3] = 1.0f;
+  std::memcpy(p, &d, sizeof(d));
   // lighting_pass.comp:200-207: constants of the shader, no uniforms
   p->ka = 0.1f; p->kd = 0.7f; p->ks = 0.2f; p->shininess = 32.0f;
-  for (int i = 0; i < 3; i++) p->light_color[i] = 1.0f;   // LightingPass (:380)
-  cvr_light l;
-  default_light(&l);
-  for (int i = 0; i < 3; i++) p->light_pos[i] = l.position[i];   // LightingPass (:372)
-  p->exposure = 1.0f;                            // Redraw (:752-753)
-  p->gamma = 2.2f;
   for (int i = 0; i < 4; i++) p->gbuffer_clear[i] = 1.0f;   // Redraw's glClearColor (:724)
   p->flow_speed = 1.0f;                          // AdvancedDeferredShading.h:129-133
   p->flow_scale = 10.0f;
@@ -247,12 +214,11 @@ void cvr_advdeferred_params_default(cvr_advdeferred_params* p) {
 cvr_status cvr_render_advdeferred(cvr_ctx* ctx, const cvr_frame* f, const cvr_advdeferred_params* p,
                                   const cvr_output* o) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
   const char* who = "cvr_render_advdeferred";
-  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
-  if (!f || !p || !o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  const cvr_deferred_params g = march_params(p);
-  cvr_status st = deferred_check_output(c, who, o);
+  cvr_status st = deferred_entry(c, who, f && p && o);
+  if (st != CVR_OK) return st;
+  const cvr_deferred_params g = deferred_prefix(p);
+  st = deferred_check_output(c, who, o);
   if (st == CVR_OK) st = check_shade_params(c, who, p);
   if (st == CVR_OK) st = deferred_check_geometry_call(c, who, f, &g);
   if (st != CVR_OK) return st;
@@ -264,35 +230,31 @@ cvr_status cvr_render_advdeferred(cvr_ctx* ctx, const cvr_frame* f, const cvr_ad
 
 cvr_status cvr_advdeferred_curvature(cvr_ctx* ctx, const cvr_frame* f, const cvr_advdeferred_params* p) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
   const char* who = "cvr_advdeferred_curvature";
-  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
-  if (!f || !p) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
+  cvr_status st = deferred_entry(c, who, f && p);
+  if (st != CVR_OK) return st;
   if (f->nranks > 1)
     return fail(c, CVR_ERR_ARG, "%s: the pass reads neighbouring pixels: whole frames only (nranks <= 1)", who);
   if (f->camera.fovy_deg != f->camera.fovy_deg || f->camera.aspect != f->camera.aspect)
     return fail(c, CVR_ERR_ARG, "%s: the camera's field of view or aspect is NaN", who);
-  const cvr_status st = check_shade_params(c, who, p);
+  st = check_shade_params(c, who, p);
+  if (st == CVR_OK)
+    st = deferred_check_kept(c, who, c->deferred.valid, "no G-buffer (cvr_deferred_geometry)", f->width, f->height,
+                             CVR_ERR_STATE);
   if (st != CVR_OK) return st;
-  if (!c->deferred.valid) return fail(c, CVR_ERR_STATE, "%s: no G-buffer (cvr_deferred_geometry)", who);
-  if (f->width != c->deferred.W || f->height != c->deferred.H)
-    return fail(c, CVR_ERR_STATE, "%s: the G-buffer is %dx%d", who, c->deferred.W, c->deferred.H);
   return curvature_pass(c, who, f);
 }
 
 cvr_status cvr_advdeferred_shade(cvr_ctx* ctx, int width, int height, const cvr_advdeferred_params* p,
                                  const cvr_output* o) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
   const char* who = "cvr_advdeferred_shade";
-  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
-  if (!p || !o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  cvr_status st = deferred_check_output(c, who, o);
+  cvr_status st = deferred_entry(c, who, p && o);
+  if (st == CVR_OK) st = deferred_check_output(c, who, o);
   if (st == CVR_OK) st = check_shade_params(c, who, p);
-  if (st != CVR_OK) return st;
-  if (!c->deferred.valid || !c->adv.valid)
-    return fail(c, CVR_ERR_STATE, "%s: no curvature planes of the kept G-buffer (cvr_advdeferred_curvature)", who);
-  st = check_viewport(c, who, width, height);
+  if (st == CVR_OK)
+    st = deferred_check_kept(c, who, c->deferred.valid && c->adv.valid,
+                             "no curvature planes of the kept G-buffer (cvr_advdeferred_curvature)", width, height);
   if (st != CVR_OK) return st;
   return shade_pass(c, p, o);
 }
@@ -304,9 +266,8 @@ cvr_status cvr_advdeferred_read_curvature(cvr_ctx* ctx, int width, int height, f
   const char* who = "cvr_advdeferred_read_curvature";
   if (!out_k1 || !out_k2 || !out_dir) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
   if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context", who);
-  if (!c->deferred.valid || !c->adv.valid)
-    return fail(c, CVR_ERR_STATE, "%s: no curvature planes (cvr_advdeferred_curvature)", who);
-  const cvr_status st = check_viewport(c, who, width, height);
+  const cvr_status st = deferred_check_kept(c, who, c->deferred.valid && c->adv.valid,
+                                            "no curvature planes (cvr_advdeferred_curvature)", width, height);
   if (st != CVR_OK) return st;
   const size_t npix = (size_t)width * height;
   std::vector<float> packed(npix * 4);

@@ -147,8 +147,7 @@ static cvr_status set_volume_common(Ctx* c, const void* src, bool src_device, in
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) {
     free_dev(c->d_cells); c->cells_bytes = 0;
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,
-                "cvr_set_volume: %s", hipGetErrorString(e));
+    return fail_hip(c, "cvr_set_volume", e);
   }
   return CVR_OK;
 }
@@ -438,8 +437,7 @@ cvr_status cvr_set_gradient(cvr_ctx* ctx, int mode) {
   (void)hipFree(tmp);
   if (e != hipSuccess) {
     free_dev(c->d_grad); c->grad_bytes = 0;
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "cvr_set_gradient: %s",
-                hipGetErrorString(e));
+    return fail_hip(c, "cvr_set_gradient", e);
   }
   c->grad_mode = mode;
   return CVR_OK;

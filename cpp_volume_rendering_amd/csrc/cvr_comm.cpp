@@ -35,7 +35,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cvr_internal.h"
+#include "cvr_host.h"
 
 using cvr::Ctx;
 
@@ -109,9 +109,7 @@ cvr_status cfail(Ctx* c, cvr_status st, const char* fmt, ...) {
 #define CHIP(ctx, expr)                                                                  \
   do {                                                                                   \
     hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess)                                                                \
-      return cfail(ctx, _e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,           \
-                   "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
+    if (_e != hipSuccess) return ::cvr::fail_hip(ctx, #expr, _e, __FILE__, __LINE__);    \
   } while (0)
 
 #define CNCCL(ctx, expr)                                                                 \

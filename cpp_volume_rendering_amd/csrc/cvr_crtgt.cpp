@@ -54,8 +54,7 @@ static cvr_status crtgt_reserve(Ctx* c, size_t npix, int job_f4, size_t nrays) {
   if (e == hipSuccess) e = hipMalloc((void**)&g.d_rays, std::max<size_t>(ray_cap, 1) * 12);
   if (e != hipSuccess) {
     crtgt_release(c);
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "cvr_crtgt_begin: %s",
-                hipGetErrorString(e));
+    return fail_hip(c, "cvr_crtgt_begin", e);
   }
   g.npix = npix;
   g.job_f4 = job_f4;

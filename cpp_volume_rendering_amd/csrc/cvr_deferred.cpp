@@ -1,5 +1,8 @@
 // cvr_deferred.cpp — deferred isosurface shading (DeferredShading; deferred.hip): the
-// argument checks, the context's G-buffer, and the geometry / shade passes of a frame.
+// argument checks, the context's G-buffer, and the geometry / shade passes of a frame;
+// and what AdvancedDeferredShading (cvr_advdeferred.cpp) has in common with it: the
+// start of an entry, the common defaults, the lighting checks, the check of a call over
+// the kept G-buffer (declared in cvr_host.h, next to the shade passes' shared frame).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -26,27 +29,62 @@ bool any_nan(const float* v, int n) {
     if (v[i] != v[i]) return true;
   return false;
 }
-bool any_negative(const float* v, int n) {
+static bool any_negative(const float* v, int n) {
   for (int i = 0; i < n; i++)
     if (v[i] < 0.0f) return true;
   return false;
 }
 
-}  // namespace cvr
+cvr_status deferred_entry(Ctx* c, const char* who, bool args_given) {
+  if (!c) return CVR_ERR_ARG;
+  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
+  if (!args_given) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
+  return CVR_OK;
+}
 
-namespace {
-
-// What the shade pass reads of the parameters (cvr_powf is specified for x >= 0).
-cvr_status check_shade_params(Ctx* c, const char* who, const cvr_deferred_params* p) {
+// What a shade pass reads of the parameters (cvr_powf is specified for x >= 0).
+cvr_status deferred_check_lighting(Ctx* c, const char* who, const cvr_deferred_params* p, const char* nan_what,
+                                   bool more_nan) {
   const float scalars[] = {p->ka, p->kd, p->ks, p->shininess, p->exposure, p->gamma};
-  if (any_nan(scalars, 6) || any_nan(p->color, 4) || any_nan(p->light_color, 3) || any_nan(p->light_pos, 3))
-    return fail(c, CVR_ERR_ARG, "%s: a lighting or tone-map parameter is NaN", who);
+  if (more_nan || any_nan(scalars, 6) || any_nan(p->color, 4) || any_nan(p->light_color, 3) ||
+      any_nan(p->light_pos, 3))
+    return fail(c, CVR_ERR_ARG, "%s: a %s parameter is NaN", who, nan_what);
   if (p->ka < 0.0f || p->kd < 0.0f || p->ks < 0.0f)
     return fail(c, CVR_ERR_ARG, "%s: ka, kd and ks must be >= 0", who);
   if (any_negative(p->color, 4) || any_negative(p->light_color, 3))
     return fail(c, CVR_ERR_ARG, "%s: the colour and the light colour must be >= 0", who);
   return CVR_OK;
 }
+
+cvr_status deferred_check_kept(Ctx* c, const char* who, bool kept, const char* missing, int width, int height,
+                               cvr_status mismatch) {
+  if (!kept) return fail(c, CVR_ERR_STATE, "%s: %s", who, missing);
+  if (width != c->deferred.W || height != c->deferred.H)
+    return fail(c, mismatch, "%s: the G-buffer is %dx%d", who, c->deferred.W, c->deferred.H);
+  return CVR_OK;
+}
+
+// The constructor's march (DeferredShading.cpp:123-127, AdvancedDeferredShading.cpp:124-128),
+// Init's blocks (:348, :561), LightingPass's light (:216, :372-380), Redraw's tone map
+// (:538-539, :752-753)
+void deferred_common_defaults(cvr_deferred_params* p) {
+  p->isovalue = 0.5f;
+  p->step_small = 0.05f;
+  p->step_large = 1.0f;
+  p->step_range = 0.1f;
+  for (int i = 0; i < 3; i++) p->num_blocks[i] = 4;
+  p->color[0] = 0.66f; p->color[1] = 0.6f; p->color[2] = 0.05f; p->color[3] = 1.0f;
+  for (int i = 0; i < 3; i++) p->light_color[i] = 1.0f;
+  cvr_light l;
+  default_light(&l);
+  for (int i = 0; i < 3; i++) p->light_pos[i] = l.position[i];
+  p->exposure = 1.0f;
+  p->gamma = 2.2f;
+}
+
+}  // namespace cvr
+
+namespace {
 
 // What the geometry pass reads of them.
 cvr_status check_geometry_params(Ctx* c, const char* who, const cvr_deferred_params* p) {
@@ -113,8 +151,7 @@ cvr_status deferred_geometry_pass(Ctx* c, const char* who, const cvr_frame* f, c
     QUIESCE(c);   // an earlier frame may still read the planes
     deferred_drop(c);
     hipError_t e = hipMalloc((void**)&D.d_gbuf, npix * 32);
-    if (e != hipSuccess)
-      return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (e != hipSuccess) return fail_hip(c, who, e);
     D.W = f->width;
     D.H = f->height;
     D.bytes = npix * 32;
@@ -145,32 +182,12 @@ namespace {
 cvr_status shade_pass(Ctx* c, const cvr_deferred_params* p, const cvr_output* o) {
   const Ctx::Deferred& D = c->deferred;
   DeferredShadeArgs S{};
-  S.W = D.W;
-  S.H = D.H;
-  for (int i = 0; i < 3; i++) {
-    S.eye[i] = D.eye[i];
-    S.light[i] = p->light_pos[i];
-    S.light_color[i] = p->light_color[i];
-  }
+  fill_shade_lighting(S, D, p);
   for (int i = 0; i < 4; i++) S.color[i] = p->color[i];
-  S.ka = p->ka;
-  S.kd = p->kd;
-  S.ks = p->ks;
-  S.shininess = p->shininess;
-  S.exposure = p->exposure;
-  S.gamma = p->gamma;
-  const size_t npix = (size_t)D.W * D.H;
   HIP_TRY(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  FrameOut fo;
-  cvr_status st = bind_frame_output(c, o, npix, fo);
-  if (st == CVR_OK) st = frame_counters_begin(c, o, 1, s, fo);
-  if (st != CVR_OK) return st;
-  st = timed_launch(c, s, [&] {
+  return shade_frame(c, o, [](hipStream_t) { return CVR_OK; }, [&](const FrameOut& fo, hipStream_t s) {
     return launch_deferred_shade(S, D.d_gbuf, fo.d_out, fo.half, fo.d_samples, fo.d_total, s);
   });
-  if (st != CVR_OK) return st;
-  return frame_output_finish(c, o, fo, s);
 }
 
 }  // namespace
@@ -181,31 +198,18 @@ extern "C" {
 void cvr_deferred_params_default(cvr_deferred_params* p) {
   if (!p) return;
   *p = cvr_deferred_params{};
-  p->isovalue = 0.5f;                            // constructor (DeferredShading.cpp:123-127)
-  p->step_small = 0.05f;
-  p->step_large = 1.0f;
-  p->step_range = 0.1f;
-  for (int i = 0; i < 3; i++) p->num_blocks[i] = 4;   // Init (:348)
-  p->color[0] = 0.66f; p->color[1] = 0.6f; p->color[2] = 0.05f; p->color[3] = 1.0f;
+  deferred_common_defaults(p);
   // Update's uniforms (:477-480) are the ones BindUniforms binds; renderingparameters.cpp:23-26
   p->ka = 0.5f; p->kd = 0.5f; p->ks = 0.8f; p->shininess = 30.0f;
-  for (int i = 0; i < 3; i++) p->light_color[i] = 1.0f;   // LightingPass (:216)
-  cvr_light l;
-  default_light(&l);
-  for (int i = 0; i < 3; i++) p->light_pos[i] = l.position[i];
-  p->exposure = 1.0f;                            // Redraw (:538-539)
-  p->gamma = 2.2f;
   p->gbuffer_clear[0] = p->gbuffer_clear[1] = p->gbuffer_clear[2] = 1.0f;   // WHITE_BACKGROUND
   p->gbuffer_clear[3] = 0.0f;
 }
 
 cvr_status cvr_deferred_geometry(cvr_ctx* ctx, const cvr_frame* f, const cvr_deferred_params* p) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
   const char* who = "cvr_deferred_geometry";
-  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
-  if (!f || !p) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  const cvr_status st = deferred_check_geometry_call(c, who, f, p);
+  cvr_status st = deferred_entry(c, who, f && p);
+  if (st == CVR_OK) st = deferred_check_geometry_call(c, who, f, p);
   if (st != CVR_OK) return st;
   return deferred_geometry_pass(c, who, f, p);
 }
@@ -213,28 +217,23 @@ cvr_status cvr_deferred_geometry(cvr_ctx* ctx, const cvr_frame* f, const cvr_def
 cvr_status cvr_deferred_shade(cvr_ctx* ctx, int width, int height, const cvr_deferred_params* p,
                               const cvr_output* o) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
   const char* who = "cvr_deferred_shade";
-  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
-  if (!p || !o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  cvr_status st = deferred_check_output(c, who, o);
-  if (st == CVR_OK) st = check_shade_params(c, who, p);
+  cvr_status st = deferred_entry(c, who, p && o);
+  if (st == CVR_OK) st = deferred_check_output(c, who, o);
+  if (st == CVR_OK) st = deferred_check_lighting(c, who, p);
+  if (st == CVR_OK)
+    st = deferred_check_kept(c, who, c->deferred.valid, "no G-buffer (cvr_deferred_geometry)", width, height);
   if (st != CVR_OK) return st;
-  if (!c->deferred.valid) return fail(c, CVR_ERR_STATE, "%s: no G-buffer (cvr_deferred_geometry)", who);
-  if (width != c->deferred.W || height != c->deferred.H)
-    return fail(c, CVR_ERR_ARG, "%s: the G-buffer is %dx%d", who, c->deferred.W, c->deferred.H);
   return shade_pass(c, p, o);
 }
 
 cvr_status cvr_render_deferred(cvr_ctx* ctx, const cvr_frame* f, const cvr_deferred_params* p,
                                const cvr_output* o) {
   Ctx* c = reinterpret_cast<Ctx*>(ctx);
-  if (!c) return CVR_ERR_ARG;
   const char* who = "cvr_render_deferred";
-  if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context (cvr_create_group)", who);
-  if (!f || !p || !o) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
-  cvr_status st = deferred_check_output(c, who, o);
-  if (st == CVR_OK) st = check_shade_params(c, who, p);
+  cvr_status st = deferred_entry(c, who, f && p && o);
+  if (st == CVR_OK) st = deferred_check_output(c, who, o);
+  if (st == CVR_OK) st = deferred_check_lighting(c, who, p);
   if (st == CVR_OK) st = deferred_check_geometry_call(c, who, f, p);
   if (st != CVR_OK) return st;
   st = deferred_geometry_pass(c, who, f, p);
@@ -250,8 +249,8 @@ cvr_status cvr_deferred_read_gbuffer(cvr_ctx* ctx, int width, int height, float*
   if (!out_position || !out_normal) return fail(c, CVR_ERR_ARG, "%s: null argument", who);
   if (c->group) return fail(c, CVR_ERR_ARG, "%s: not available on a group context", who);
   const Ctx::Deferred& D = c->deferred;
-  if (!D.valid) return fail(c, CVR_ERR_STATE, "%s: no G-buffer (cvr_deferred_geometry)", who);
-  if (width != D.W || height != D.H) return fail(c, CVR_ERR_ARG, "%s: the G-buffer is %dx%d", who, D.W, D.H);
+  const cvr_status st = deferred_check_kept(c, who, D.valid, "no G-buffer (cvr_deferred_geometry)", width, height);
+  if (st != CVR_OK) return st;
   const size_t npix = (size_t)D.W * D.H;
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));

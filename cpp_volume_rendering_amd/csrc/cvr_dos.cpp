@@ -216,8 +216,7 @@ cvr_status cvr_set_extinction_volume(cvr_ctx* ctx, const float* tf_rgba, int n, 
   (void)hipFree(d_tf);
   if (e != hipSuccess) {
     ext_drop(c);
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,
-                "cvr_set_extinction_volume: %s", hipGetErrorString(e));
+    return fail_hip(c, "cvr_set_extinction_volume", e);
   }
   for (int i = 0; i < 3; i++) c->ext.res[i] = res[i];
   c->ext.levels = nl;

@@ -191,8 +191,7 @@ cvr_status cvr_set_extinction_sat(cvr_ctx* ctx, const float* ext_lut, int lut_n)
     if (x) (void)hipEventDestroy(x);
   if (e != hipSuccess) {
     sat_drop(c);
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,
-                "cvr_set_extinction_sat: %s", hipGetErrorString(e));
+    return fail_hip(c, "cvr_set_extinction_sat", e);
   }
   c->sat.dims[0] = w; c->sat.dims[1] = h; c->sat.dims[2] = d;
   return CVR_OK;

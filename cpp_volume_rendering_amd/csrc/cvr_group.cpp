@@ -23,7 +23,7 @@
 #include <cstring>
 #include <vector>
 
-#include "cvr_internal.h"
+#include "cvr_host.h"
 
 using cvr::Ctx;
 
@@ -66,9 +66,7 @@ cvr_status gfail(Ctx* c, cvr_status st, const char* fmt, ...) {
 #define GHIP(ctx, expr)                                                                  \
   do {                                                                                   \
     hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess)                                                                \
-      return gfail(ctx, _e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,           \
-                   "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);  \
+    if (_e != hipSuccess) return ::cvr::fail_hip(ctx, #expr, _e, __FILE__, __LINE__);    \
   } while (0)
 
 // a member's failure, reported on the group with the member's message

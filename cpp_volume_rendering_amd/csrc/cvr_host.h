@@ -1,8 +1,11 @@
 // cvr_host.h — what the C-ABI translation units (cvr_api.cpp, cvr_options.cpp,
 // cvr_rc1pass.cpp, cvr_dos.cpp, cvr_ebs.cpp, cvr_lightcache.cpp, cvr_crtgt.cpp,
-// cvr_vct.cpp, cvr_sbtm.cpp, cvr_deferred.cpp, cvr_advdeferred.cpp, cvr_iso.cpp) share: error reporting, device-memory helpers, the half and vector helpers of
-// the host arithmetic, and the frame set-up common to the renderers.  Host only:
-// never included by a .hip file or a kernel header.
+// cvr_vct.cpp, cvr_sbtm.cpp, cvr_deferred.cpp, cvr_advdeferred.cpp, cvr_iso.cpp) share:
+// error reporting (fail, and fail_hip with the one mapping of a HIP error to a status,
+// which cvr_comm.cpp and cvr_group.cpp take from here too), device-memory helpers, the
+// half and vector helpers of the host arithmetic, the frame set-up and the frame-output
+// path common to the renderers, and what the two deferred renderers share on the host.
+// Host only: never included by a .hip file or a kernel header.
 //
 // Compiled with -ffp-contract=off: the arithmetic below feeds the kernels and
 // must be bit-reproducible (CVR-SPEC).
@@ -20,12 +23,18 @@ namespace cvr {
 // Stores the message in the context (cvr_last_error) and returns st.
 cvr_status fail(Ctx* c, cvr_status st, const char* fmt, ...);
 
-#define HIP_TRY(ctx, expr)                                                                    \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess)                                                                     \
-      return ::cvr::fail(ctx, _e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP,          \
-                         "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+// A failed HIP call as a status and a message, "<who>: <HIP's text>" and, with `file`,
+// " (<file>:<line>)": out of memory is CVR_ERR_OOM, everything else CVR_ERR_HIP.
+inline cvr_status fail_hip(Ctx* c, const char* who, hipError_t e, const char* file = nullptr, int line = 0) {
+  const cvr_status st = e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP;
+  if (!file) return fail(c, st, "%s: %s", who, hipGetErrorString(e));
+  return fail(c, st, "%s: %s (%s:%d)", who, hipGetErrorString(e), file, line);
+}
+
+#define HIP_TRY(ctx, expr)                                                     \
+  do {                                                                         \
+    hipError_t _e = (expr);                                                    \
+    if (_e != hipSuccess) return ::cvr::fail_hip(ctx, #expr, _e, __FILE__, __LINE__); \
   } while (0)
 
 // Before a state change writes or frees device state that frames read (volume
@@ -148,14 +157,27 @@ cvr_status ensure_iso_blocks(Ctx* c, const int nb[3]);
 // cvr_deferred.cpp: the G-buffer goes with the volume (and with another viewport);
 // the context's end also frees its hit counter
 void deferred_drop(Ctx* c, bool destroy = false);
-// cvr_deferred.cpp, for the renderers over its G-buffer (cvr_advdeferred.cpp): the
-// checks of a call that marches `f`, the geometry pass into the context's G-buffer on
-// the context stream, and the check of an output's buffer and format
+// cvr_deferred.cpp, for the renderers over its G-buffer (cvr_advdeferred.cpp).
+// cvr_advdeferred_params begins with the fields of cvr_deferred_params (include/cvr.h;
+// deferred_prefix, checked at compile time), so what the two renderers have in common
+// takes a cvr_deferred_params: the start of an entry (a context that is no group, no
+// null argument), the common defaults (everything but ka .. shininess and
+// gbuffer_clear), the lighting checks (`nan_what` names the parameters in the NaN
+// message, `more_nan`: one of the caller's own is NaN), the checks of a call that
+// marches `f`, the geometry pass into the context's G-buffer on the context stream,
+// the check of an output's buffer and format, and the check of a call over the kept
+// G-buffer (`kept`: it is there, else CVR_ERR_STATE with `missing`; another size than
+// width x height is `mismatch`)
 bool any_nan(const float* v, int n);
-bool any_negative(const float* v, int n);
+cvr_status deferred_entry(Ctx* c, const char* who, bool args_given);
+void deferred_common_defaults(cvr_deferred_params* p);
+cvr_status deferred_check_lighting(Ctx* c, const char* who, const cvr_deferred_params* p,
+                                   const char* nan_what = "lighting or tone-map", bool more_nan = false);
 cvr_status deferred_check_geometry_call(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p);
 cvr_status deferred_geometry_pass(Ctx* c, const char* who, const cvr_frame* f, const cvr_deferred_params* p);
 cvr_status deferred_check_output(Ctx* c, const char* who, const cvr_output* o);
+cvr_status deferred_check_kept(Ctx* c, const char* who, bool kept, const char* missing, int width, int height,
+                               cvr_status mismatch = CVR_ERR_ARG);
 // cvr_advdeferred.cpp: the curvature planes go with the G-buffer (deferred_drop calls
 // this); the context's end also frees the lighting pass's tables and its counter
 void advdeferred_drop(Ctx* c, bool destroy = false);
@@ -222,6 +244,41 @@ cvr_status timed_launch(Ctx* c, hipStream_t s, const Launch& launch) {
     c->timed_frames++;
   }
   return CVR_OK;
+}
+
+// The lighting fields DeferredShadeArgs and AdvShadeArgs share, from the kept G-buffer
+// and the parameters' common part.
+template <class Args>
+void fill_shade_lighting(Args& S, const Ctx::Deferred& D, const cvr_deferred_params* p) {
+  S.W = D.W;
+  S.H = D.H;
+  for (int i = 0; i < 3; i++) {
+    S.eye[i] = D.eye[i];
+    S.light[i] = p->light_pos[i];
+    S.light_color[i] = p->light_color[i];
+  }
+  S.ka = p->ka;
+  S.kd = p->kd;
+  S.ks = p->ks;
+  S.shininess = p->shininess;
+  S.exposure = p->exposure;
+  S.gamma = p->gamma;
+}
+
+// A lighting pass over the kept G-buffer as a frame of that path (one "tile": the
+// kernel adds its counts to the total itself): before(s) on the stream once the
+// counters are ready, then launch(fo, s) between the timing events.
+template <class Before, class Launch>
+cvr_status shade_frame(Ctx* c, const cvr_output* o, const Before& before, const Launch& launch) {
+  const size_t npix = (size_t)c->deferred.W * c->deferred.H;
+  hipStream_t s = c->stream;
+  FrameOut fo;
+  cvr_status st = bind_frame_output(c, o, npix, fo);
+  if (st == CVR_OK) st = frame_counters_begin(c, o, 1, s, fo);
+  if (st == CVR_OK) st = before(s);
+  if (st == CVR_OK) st = timed_launch(c, s, [&] { return launch(fo, s); });
+  if (st != CVR_OK) return st;
+  return frame_output_finish(c, o, fo, s);
 }
 
 // A shaded renderer's frame over that path: launch(out, samples, shade,

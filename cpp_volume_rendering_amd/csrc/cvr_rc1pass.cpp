@@ -182,8 +182,7 @@ cvr_status ensure_cell_flags(Ctx* c) {
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(t);
   if (e != hipSuccess)
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "cell flags: %s",
-                hipGetErrorString(e));
+    return fail_hip(c, "cell flags", e);
   c->skip.flags_valid = 1;
   c->skip.flags_set = 1;
   return CVR_OK;

@@ -174,7 +174,7 @@ cvr_status cvr_render_sbtm(cvr_ctx* ctx, const cvr_frame* f, const cvr_sbtm_para
     hipError_t e = hipMalloc((void**)&B.d_occ, npix * 8);   // two sets of two planes
     if (e != hipSuccess) {
       sbtm_drop(c);
-      return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+      return fail_hip(c, who, e);
     }
     B.npix = npix;
     B.bytes = npix * 16;

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <vector>
 
@@ -110,8 +111,9 @@ static cvr_status build_pyramid(Ctx* c, const char* who) {
   if (e != hipSuccess) {
     free_dev(v.d_pyr);
     free_dev(v.d_levels);
-    return fail(c, e == hipErrorOutOfMemory ? CVR_ERR_OOM : CVR_ERR_HIP, "%s: pyramid: %s", who,
-                hipGetErrorString(e));
+    char what[64];
+    std::snprintf(what, sizeof(what), "%s: pyramid", who);
+    return fail_hip(c, what, e);
   }
   std::memcpy(v.levels, lv, sizeof(lv));
   v.nl = nl;

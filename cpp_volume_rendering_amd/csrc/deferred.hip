@@ -11,8 +11,11 @@
 // One lane per ray (8x8 tile per wave, the iso.hip tiling).  The march is the loop of
 // rc1pisodfscustom (iso.hip variant 1) up to its first hit: the same skip test with an
 // epsilon of 0.001, the same exit distance with up to three 1e-4 offsets, the step from
-// the current density, the hit refined as t - h * (1 - tt); it shares iso.hip's volume
-// fetch, block index and block-table fetch (iso_common.h).  Every GLSL float expression
+// the current density, the hit refined as t - h * (1 - tt); the volume fetch, the block
+// index, the block-table fetch, the ray's reciprocal and the exit distance are
+// iso_common.h's, and what the shade pass has in common with advdeferred.hip's (the
+// G-buffer fetch, the Blinn-Phong terms, the tone map, the pixel's stores and counts) is
+// gbuffer_common.h's.  Every GLSL float expression
 // is evaluated in the shader's order without contraction (-ffp-contract=off), as
 // tests/support/deferred_ref.cpp does.  Reproduced as written: a ray that
 // misses the box keeps the G-buffer's clear value and is lit; normalize(0) is NaN and
@@ -60,15 +63,8 @@ __device__ int deferred_march(const IsoArgs& Q, const uint4* __restrict__ cells,
   const float tfar = r.tfar;
   const float iso = Q.iso;
   SamplePos sp;
-  // rayDirRecip (:91-94), per ray
   float rdir[3];
-  {
-    const float dd[3] = {dir.x, dir.y, dir.z};
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-      rdir[i] = fabsf(dd[i]) > 1e-6f ? 1.0f / dd[i]
-                                     : (dd[i] > 0.0f ? 1e6f : (dd[i] < 0.0f ? -1e6f : 0.0f));
-  }
+  iso_ray_recip(dir, rdir);   // rayDirRecip (:91-94), per ray
   float t = r.tnear;
   float dc = iso_density(A, cells, iso_tex(eye, dir, t, hg), sp);   // prevDensity at tnear (:163)
   fetches++;
@@ -80,21 +76,9 @@ __device__ int deferred_march(const IsoArgs& Q, const uint4* __restrict__ cells,
     iso_block(Q, eye, dir, t, b);
     const float2 m = iso_block_range(Q, mm, b);
     if (iso < m.x - 0.001f || iso > m.y + 0.001f) {   // isBlockSkippable (:130-136)
-      // calculateNextBlockIntersection (:89-129) from the current position: the exit
-      // distance of the block (getBlockBounds from the unwrapped index) plus offsets
+      // calculateNextBlockIntersection (:89-129) from the current position
       const float op[3] = {fmaf(dir.x, t, eye.x), fmaf(dir.y, t, eye.y), fmaf(dir.z, t, eye.z)};
-      float tmax[3];
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        const float bmin = Q.nhg[i] + Q.bs[i] * (float)b[i];
-        const float bmax = bmin + Q.bs[i];
-        tmax[i] = fmaxf((bmin - op[i]) * rdir[i], (bmax - op[i]) * rdir[i]);
-      }
-      float exitT = fminf(fminf(tmax[0], tmax[1]), tmax[2]);
-      if (fabsf(exitT - tmax[0]) < 1e-5f) exitT += 1e-4f;
-      if (fabsf(exitT - tmax[1]) < 1e-5f) exitT += 1e-4f;
-      if (fabsf(exitT - tmax[2]) < 1e-5f) exitT += 1e-4f;
-      t += fmaxf(Q.step_small, exitT);
+      t += fmaxf(Q.step_small, iso_block_exit(Q, b, op, rdir));
       // prevDensity = texture(newPos) (:184): fetched by the shader, overwritten before use
       fetches++;
       have = false;
@@ -162,51 +146,30 @@ deferred_shade_kernel(DeferredShadeArgs Q, const float4* __restrict__ gbuf, floa
                       int half, uint32_t* __restrict__ samples, unsigned long long* __restrict__ total) {
   const long long npix = (long long)Q.W * Q.H;
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool inside = i < npix;
   uint32_t count = 0;
-  if (i < npix) {
-    const int py = (int)(i / Q.W), px = (int)(i - (long long)py * Q.W);
-    const long long g = (long long)edge_texel(py, Q.H) * Q.W + edge_texel(px, Q.W);
-    const float4 gp = gbuf[g], gn = gbuf[npix + g];
-    count = __float_as_uint(gbuf[npix + i].w);
-    const f3 pos{gp.x, gp.y, gp.z}, n{gn.x, gn.y, gn.z};
-    float4 c;
+  float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (inside) {
+    const GBufferPixel g = gbuffer_fetch(gbuf, Q.W, Q.H, npix, i);
+    count = g.count;
+    const f3 pos = g.pos, n = g.raw;
     if (length3(pos) < 0.001f || length3(n) < 0.001f) {
       c = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
     } else {
-      const f3 L = normalize3(f3{Q.light[0] - pos.x, Q.light[1] - pos.y, Q.light[2] - pos.z});
-      const f3 V = normalize3(f3{Q.eye[0] - pos.x, Q.eye[1] - pos.y, Q.eye[2] - pos.z});
-      const f3 Hd = normalize3(f3{L.x + V.x, L.y + V.y, L.z + V.z});
-      const float diff = fmaxf(dot3(n, L), 0.0f);
-      const float spec = cvr_powf(fmaxf(dot3(n, Hd), 0.0f), Q.shininess);
+      const PhongTerms ph = gbuffer_phong(Q.light, Q.eye, pos, n, Q.shininess);
       float rgb[3];
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         const float ambient = (Q.ka * Q.light_color[k]) * Q.color[k];
-        const float diffuse = ((Q.kd * diff) * Q.light_color[k]) * Q.color[k];
-        const float specular = (Q.ks * spec) * Q.light_color[k];
+        const float diffuse = ((Q.kd * ph.diff) * Q.light_color[k]) * Q.color[k];
+        const float specular = (Q.ks * ph.spec) * Q.light_color[k];
         rgb[k] = (ambient + diffuse) + specular;
       }
       c = make_float4(rgb[0], rgb[1], rgb[2], Q.color[3]);
     }
-    // post_process.frag: the quad samples finalImage at the pixel's centre, the texel itself
-    if (Q.exposure > 0.0f) {
-      c.x = 1.0f - cvr_expf((-c.x) * Q.exposure);
-      c.y = 1.0f - cvr_expf((-c.y) * Q.exposure);
-      c.z = 1.0f - cvr_expf((-c.z) * Q.exposure);
-    }
-    if (Q.gamma > 0.0f) {
-      const float e = 1.0f / Q.gamma;
-      c.x = cvr_powf(c.x, e);
-      c.y = cvr_powf(c.y, e);
-      c.z = cvr_powf(c.z, e);
-    }
-    store_rgba(out, i, c, half);
-    if (samples) samples[i] = count;
+    tone_map(c, Q.exposure, Q.gamma);
   }
-  if (total) {
-    const unsigned long long v = wave_sum((unsigned long long)count);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(total, v);
-  }
+  gbuffer_pixel_tail(inside, out, i, c, half, samples, count, total);
 }
 
 }  // namespace
@@ -224,8 +187,8 @@ hipError_t launch_deferred_shade(const DeferredShadeArgs& q, const float4* gbuf,
                                  uint32_t* samples, unsigned long long* total, hipStream_t s) {
   const long long npix = (long long)q.W * q.H;
   if (npix <= 0) return hipSuccess;
-  hipLaunchKernelGGL(deferred_shade_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, q, gbuf, out,
-                     half, samples, total);
+  hipLaunchKernelGGL(deferred_shade_kernel, pixel_grid(npix), dim3(kPixelBlock), 0, s, q, gbuf, out, half, samples,
+                     total);
   return hipGetLastError();
 }
 

@@ -612,17 +612,49 @@ class RayCasting1Pass(BaseVolumeRenderer):
                             self.screen_width / self.screen_height)
         return make_frame(camera, self.width, self.height)
 
-    def Update(self, camera: Camera) -> bool:
+    def _begin_update(self, camera: Camera, gradient_shading=None) -> RenderingParameters:
+        """What every Update starts with: the frame, and the Blinn-Phong block of the
+        parameters as far as their struct has it (the step, the gradient-shading switch,
+        the rendering parameters' material, specular colour and light position).
+        Returns the rendering parameters."""
         rp = self.m_ext_rendering_parameters or RenderingParameters()
         self._frame = self._camera_frame(camera)
         p = self._params
-        p.step = float(self.m_u_step_size)
-        p.apply_gradient_shading = int(bool(self.m_apply_gradient_shading) and
-                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
+        if hasattr(p, "step"):
+            p.step = float(self.m_u_step_size)
+        if hasattr(p, "apply_gradient_shading"):
+            on = self.m_apply_gradient_shading if gradient_shading is None else gradient_shading
+            p.apply_gradient_shading = int(bool(on) and
+                                           self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
         p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
         p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
-        p.ispecular[:] = [float(v) for v in rp.light_specular]
-        p.light_pos[:] = [float(v) for v in rp.light_position]
+        if hasattr(p, "ispecular"):
+            p.ispecular[:] = [float(v) for v in rp.light_specular]
+        if hasattr(p, "light_pos"):
+            p.light_pos[:] = [float(v) for v in rp.light_position]
+        return rp
+
+    @staticmethod
+    def _fill_light(light: "N.Light", rp: RenderingParameters):
+        """cvr_light from the rendering parameters' light (its camera frame and spot angle)."""
+        light.position[:] = [float(v) for v in rp.light_position]
+        light.forward[:] = [float(v) for v in rp.light_forward]
+        light.up[:] = [float(v) for v in rp.light_up]
+        light.right[:] = [float(v) for v in rp.light_right]
+        light.spot_angle_deg = float(rp.spot_light_angle)
+
+    def _fill_iso_march(self):
+        """The iso march block: blocks, isovalue, the adaptive steps and the colour."""
+        p = self._params
+        p.num_blocks[:] = [int(b) for b in self.num_blocks]
+        p.isovalue = float(self.m_u_isovalue)
+        p.step_small = float(self.m_u_step_size_small)
+        p.step_large = float(self.m_u_step_size_large)
+        p.step_range = float(self.m_u_step_size_range)
+        p.color[:] = [float(c) for c in self.m_u_color]
+
+    def Update(self, camera: Camera) -> bool:
+        self._begin_update(camera)
         return True
 
     def Redraw(self, stream: Optional[torch.cuda.Stream] = None, count_samples: bool = True):
@@ -675,13 +707,20 @@ class RayCasting1Pass(BaseVolumeRenderer):
 
     # C entry of this renderer's frame (cvr_render_rc1pass / _dosct / _extbsd)
     _ENTRY = "cvr_render_rc1pass"
+    # C entry of the frame through a light cache (DOS, EBS: "Use Pre-Illumination")
+    _PREILLUM_ENTRY = None
 
     def render_to(self, frame: N.Frame, out: N.Output):
         """One frame (or this rank's screen tiles of it) into `out`, with the parameters
         of the last Update(), asynchronous on the device's current stream."""
-        N.check(getattr(N.lib(), self._ENTRY)(self.device.handle, ctypes.byref(frame),
-                                              ctypes.byref(self._params), ctypes.byref(out)),
-                self._ENTRY, self.device.handle)
+        h = self.device.handle
+        if self._PREILLUM_ENTRY and self.pre_illumination:
+            dims = (ctypes.c_int * 3)(*[int(v) for v in self.light_cache_resolution])
+            N.check(getattr(N.lib(), self._PREILLUM_ENTRY)(h, ctypes.byref(frame), ctypes.byref(self._params),
+                                                           dims, ctypes.byref(out)), self._PREILLUM_ENTRY, h)
+            return
+        N.check(getattr(N.lib(), self._ENTRY)(h, ctypes.byref(frame), ctypes.byref(self._params),
+                                              ctypes.byref(out)), self._ENTRY, h)
 
     def render_frames_to(self, frames, outs):
         """Several frames in ONE launch (cvr_render_rc1pass_frames): frames[i] into
@@ -762,20 +801,9 @@ class RC1PConeTracingDirOcclusionShading(RayCasting1Pass):
         self.SetOutdated()
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
+        rp = self._begin_update(camera)
         p = self._params
-        p.step = float(self.m_u_step_size)
-        p.apply_gradient_shading = int(bool(self.m_apply_gradient_shading) and
-                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
-        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
-        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
-        p.ispecular[:] = [float(v) for v in rp.light_specular]
-        p.light.position[:] = [float(v) for v in rp.light_position]
-        p.light.forward[:] = [float(v) for v in rp.light_forward]
-        p.light.up[:] = [float(v) for v in rp.light_up]
-        p.light.right[:] = [float(v) for v in rp.light_right]
-        p.light.spot_angle_deg = float(rp.spot_light_angle)
+        self._fill_light(p.light, rp)
         p.apply_occlusion = int(bool(self.glsl_apply_occlusion))
         p.apply_shadow = int(bool(self.glsl_apply_shadow))
         p.shadow_type = int(self.type_of_shadow)
@@ -784,15 +812,7 @@ class RC1PConeTracingDirOcclusionShading(RayCasting1Pass):
         return True
 
     _ENTRY = "cvr_render_dosct"
-
-    def render_to(self, frame: N.Frame, out: N.Output):
-        if not self.pre_illumination:
-            return super().render_to(frame, out)
-        dims = (ctypes.c_int * 3)(*[int(v) for v in self.light_cache_resolution])
-        N.check(N.lib().cvr_render_dosct_preillum(self.device.handle, ctypes.byref(frame),
-                                                  ctypes.byref(self._params), dims,
-                                                  ctypes.byref(out)),
-                "cvr_render_dosct_preillum", self.device.handle)
+    _PREILLUM_ENTRY = "cvr_render_dosct_preillum"
 
 
 class RC1PExtinctionBasedShading(RayCasting1Pass):
@@ -834,16 +854,8 @@ class RC1PExtinctionBasedShading(RayCasting1Pass):
         return True
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
+        rp = self._begin_update(camera)
         p = self._params
-        p.step = float(self.m_u_step_size)
-        p.apply_gradient_shading = int(bool(self.m_apply_gradient_shading) and
-                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
-        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
-        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
-        p.ispecular[:] = [float(v) for v in rp.light_specular]
-        p.light_pos[:] = [float(v) for v in rp.light_position]
         p.light_forward[:] = [float(v) for v in rp.light_forward]
         p.apply_occlusion = int(bool(self.apply_ambient_occlusion))
         p.occlusion_shells = int(self.ambient_occlusion_shells)
@@ -858,15 +870,7 @@ class RC1PExtinctionBasedShading(RayCasting1Pass):
         return True
 
     _ENTRY = "cvr_render_extbsd"
-
-    def render_to(self, frame: N.Frame, out: N.Output):
-        if not self.pre_illumination:
-            return super().render_to(frame, out)
-        dims = (ctypes.c_int * 3)(*[int(v) for v in self.light_cache_resolution])
-        N.check(N.lib().cvr_render_extbsd_preillum(self.device.handle, ctypes.byref(frame),
-                                                   ctypes.byref(self._params), dims,
-                                                   ctypes.byref(out)),
-                "cvr_render_extbsd_preillum", self.device.handle)
+    _PREILLUM_ENTRY = "cvr_render_extbsd_preillum"
 
 
 class RC1PVoxelConeTracingSGPU(RayCasting1Pass):
@@ -903,20 +907,9 @@ class RC1PVoxelConeTracingSGPU(RayCasting1Pass):
         return True
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
+        rp = self._begin_update(camera)
         p = self._params
-        p.step = float(self.m_u_step_size)
-        p.apply_gradient_shading = int(bool(self.m_apply_gradient_shading) and
-                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
-        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
-        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
-        p.ispecular[:] = [float(v) for v in rp.light_specular]
-        p.light.position[:] = [float(v) for v in rp.light_position]
-        p.light.forward[:] = [float(v) for v in rp.light_forward]
-        p.light.up[:] = [float(v) for v in rp.light_up]
-        p.light.right[:] = [float(v) for v in rp.light_right]
-        p.light.spot_angle_deg = float(rp.spot_light_angle)
+        self._fill_light(p.light, rp)
         p.apply_occlusion = int(bool(self.apply_ambient_occlusion))
         p.apply_shadow = int(bool(self.apply_voxel_cone_tracing))
         p.cone_step = float(self.cone_step_size)
@@ -1047,8 +1040,6 @@ class RC1PConeLightGroundTruthSteps(RayCasting1Pass):
         self.SetOutdated()
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
         if self.m_light_parameters_outdated or self.occ_rays is None:
             self.occ_rays, self.sdw_rays = build_crtgt_rays(
                 self.m_occ_cone_aperture_angle, self.m_occ_num_rays_sampled,
@@ -1056,16 +1047,8 @@ class RC1PConeLightGroundTruthSteps(RayCasting1Pass):
             self.m_light_parameters_outdated = False
         p = self._params
         N.lib().cvr_crtgt_params_default(ctypes.byref(p))
-        p.step = float(self.m_u_step_size)
-        p.apply_gradient_shading = int(bool(self.m_apply_gradient) and
-                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
-        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
-        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
-        p.light.position[:] = [float(v) for v in rp.light_position]
-        p.light.forward[:] = [float(v) for v in rp.light_forward]
-        p.light.up[:] = [float(v) for v in rp.light_up]
-        p.light.right[:] = [float(v) for v in rp.light_right]
-        p.light.spot_angle_deg = float(rp.spot_light_angle)
+        rp = self._begin_update(camera, gradient_shading=self.m_apply_gradient)
+        self._fill_light(p.light, rp)
         p.light_gap = float(self.m_u_light_ray_initial_step)
         p.light_step = float(self.m_u_light_ray_step_size)
         p.apply_occlusion = int(bool(self.m_apply_occlusion))
@@ -1129,22 +1112,9 @@ class RayCasting1PassIsoAdapt(RayCasting1Pass):
         return True
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
-        p = self._params
-        p.variant = self.VARIANT
-        p.num_blocks[:] = [int(b) for b in self.num_blocks]
-        p.isovalue = float(self.m_u_isovalue)
-        p.step_small = float(self.m_u_step_size_small)
-        p.step_large = float(self.m_u_step_size_large)
-        p.step_range = float(self.m_u_step_size_range)
-        p.color[:] = [float(c) for c in self.m_u_color]
-        p.apply_gradient_shading = int(bool(self.m_apply_gradient_shading) and
-                                       self.m_ext_data_manager.gradient_type != N.GRADIENT_NONE)
-        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd
-        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
-        p.ispecular[:] = [float(v) for v in rp.light_specular]
-        p.light_pos[:] = [float(v) for v in rp.light_position]
+        self._begin_update(camera)
+        self._params.variant = self.VARIANT
+        self._fill_iso_march()
         return True
 
     def FillParameterSpace(self, pspace: dict):
@@ -1228,51 +1198,44 @@ class DeferredShading(RayCasting1PassIsoAdapt):
         return super().Init(swidth, sheight)
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
+        self._begin_update(camera)          # ka .. shininess: UpdateLightingPassUniforms (:477-482)
+        self._fill_iso_march()
         p = self._params
-        p.num_blocks[:] = [int(b) for b in self.num_blocks]
-        p.isovalue = float(self.m_u_isovalue)
-        p.step_small = float(self.m_u_step_size_small)
-        p.step_large = float(self.m_u_step_size_large)
-        p.step_range = float(self.m_u_step_size_range)
         p.gbuffer_clear[:] = [float(c) for c in self.gbuffer_clear]
-        p.color[:] = [float(c) for c in self.m_u_color]
-        p.ka, p.kd = rp.blinnphong_ka, rp.blinnphong_kd   # UpdateLightingPassUniforms (:477-482)
-        p.ks, p.shininess = rp.blinnphong_ks, rp.blinnphong_shininess
         p.light_color[:] = [float(v) for v in self.light_color]
-        p.light_pos[:] = [float(v) for v in rp.light_position]
         p.exposure, p.gamma = float(self.exposure), float(self.gamma)
-        f = self._frame
-        key = (bytes(f), tuple(p.num_blocks), p.isovalue, p.step_small, p.step_large, p.step_range,
+        key = (bytes(self._frame), tuple(p.num_blocks), p.isovalue, p.step_small, p.step_large, p.step_range,
                tuple(p.gbuffer_clear), id(self._dev))
         self._geometry_outdated = key != self._geometry_key
         self._pending_key = key
         return True
 
     def render_to(self, frame: N.Frame, out: N.Output):
+        """The shade pass alone (_SHADE_ENTRY) over the kept G-buffer when it was marched
+        from this Update's frame and march parameters, else the whole frame (_ENTRY)."""
         h = self.device.handle
         if frame is self._frame and not self._geometry_outdated:
-            N.check(N.lib().cvr_deferred_shade(h, frame.width, frame.height, ctypes.byref(self._params),
-                                               ctypes.byref(out)), "cvr_deferred_shade", h)
+            N.check(getattr(N.lib(), self._SHADE_ENTRY)(h, frame.width, frame.height, ctypes.byref(self._params),
+                                                        ctypes.byref(out)), self._SHADE_ENTRY, h)
             return
         self._geometry_key = None
-        N.check(N.lib().cvr_render_deferred(h, ctypes.byref(frame), ctypes.byref(self._params),
-                                            ctypes.byref(out)), "cvr_render_deferred", h)
+        N.check(getattr(N.lib(), self._ENTRY)(h, ctypes.byref(frame), ctypes.byref(self._params),
+                                              ctypes.byref(out)), self._ENTRY, h)
         if frame is self._frame:
             self._geometry_key = self._pending_key
             self._geometry_outdated = False
 
     def render_frames_to(self, frames, outs):
-        raise NotImplementedError("DeferredShading: one frame per call")
+        raise NotImplementedError(f"{type(self).__name__}: one frame per call")
 
     def FillParameterSpace(self, pspace: dict):
-        pspace.clear()                              # DeferredShading.cpp:545-551
+        pspace.clear()              # DeferredShading.cpp:545-551, AdvancedDeferredShading.cpp:759-765
         pspace["StepSizeSmall"] = (0.01, 0.25, 0.05)
         pspace["StepSizeLarge"] = (0.25, 2.0, 0.25)
         pspace["StepSizeRange"] = (0.05, 0.26, 0.05)
 
     _ENTRY = "cvr_render_deferred"
+    _SHADE_ENTRY = "cvr_deferred_shade"
 
 
 class AdvancedDeferredShading(DeferredShading):
@@ -1323,55 +1286,19 @@ class AdvancedDeferredShading(DeferredShading):
         return k1, k2, d
 
     def Update(self, camera: Camera) -> bool:
-        rp = self.m_ext_rendering_parameters or RenderingParameters()
-        self._frame = self._camera_frame(camera)
+        super().Update(camera)              # the march, the light (LightingPass :372), the tone map
         p = self._params
-        p.num_blocks[:] = [int(b) for b in self.num_blocks]
-        p.isovalue = float(self.m_u_isovalue)
-        p.step_small = float(self.m_u_step_size_small)
-        p.step_large = float(self.m_u_step_size_large)
-        p.step_range = float(self.m_u_step_size_range)
-        p.gbuffer_clear[:] = [float(c) for c in self.gbuffer_clear]
-        p.color[:] = [float(c) for c in self.m_u_color]
         p.ka, p.kd, p.ks, p.shininess = self.ka, self.kd, self.ks, self.shininess
-        p.light_color[:] = [float(v) for v in self.light_color]
-        p.light_pos[:] = [float(v) for v in rp.light_position]    # LightingPass (:372)
-        p.exposure, p.gamma = float(self.exposure), float(self.gamma)
         p.flow_speed, p.flow_scale = float(self.m_flow_speed), float(self.m_flow_scale)
         p.time = float(self.m_current_time)
         p.show_ridges, p.show_valleys = int(self.m_show_ridges), int(self.m_show_valleys)
         p.accessibility_strength = float(self.m_accessibility_strength)
         p.screen_size[:] = [float(v) for v in self.screen_size]
         p.colormap_s, p.colormap_v = float(self.s), float(self.v)
-        key = (bytes(self._frame), tuple(p.num_blocks), p.isovalue, p.step_small, p.step_large, p.step_range,
-               tuple(p.gbuffer_clear), id(self._dev))
-        self._geometry_outdated = key != self._geometry_key
-        self._pending_key = key
         return True
 
-    def render_to(self, frame: N.Frame, out: N.Output):
-        h = self.device.handle
-        if frame is self._frame and not self._geometry_outdated:
-            N.check(N.lib().cvr_advdeferred_shade(h, frame.width, frame.height, ctypes.byref(self._params),
-                                                  ctypes.byref(out)), "cvr_advdeferred_shade", h)
-            return
-        self._geometry_key = None
-        N.check(N.lib().cvr_render_advdeferred(h, ctypes.byref(frame), ctypes.byref(self._params),
-                                               ctypes.byref(out)), "cvr_render_advdeferred", h)
-        if frame is self._frame:
-            self._geometry_key = self._pending_key
-            self._geometry_outdated = False
-
-    def render_frames_to(self, frames, outs):
-        raise NotImplementedError("AdvancedDeferredShading: one frame per call")
-
-    def FillParameterSpace(self, pspace: dict):
-        pspace.clear()                              # AdvancedDeferredShading.cpp:759-765
-        pspace["StepSizeSmall"] = (0.01, 0.25, 0.05)
-        pspace["StepSizeLarge"] = (0.25, 2.0, 0.25)
-        pspace["StepSizeRange"] = (0.05, 0.26, 0.05)
-
     _ENTRY = "cvr_render_advdeferred"
+    _SHADE_ENTRY = "cvr_advdeferred_shade"
 
 
 def composite_over_white(rgba: np.ndarray) -> np.ndarray:
