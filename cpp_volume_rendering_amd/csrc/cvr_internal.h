@@ -482,6 +482,7 @@ struct Ctx {
   OrderSlot oslot[kOrderSlots];
   int slot_rr = 0;                 // next slot handed to a new render stream
   long long frame_no = 0;
+  int rc1pass_variant = -1;        // option "rc1pass_variant": the last rc1pass_tile_kernel launched (-1: none)
   hipStream_t side = nullptr;      // high-priority stream for the order builds
   hipEvent_t ev_frame = nullptr;   // end of a frame's ray-march (the side stream waits on it)
   int num_cus = 0;
@@ -704,10 +705,12 @@ hipError_t launch_gradient(const Ctx& c, int mode, uint2* tmp, hipStream_t s);
 hipError_t launch_selftest_arith(int e_rcp_lo, int e_rcp_n, int e_sqrt_lo, int e_sqrt_n,
                                  unsigned long long* bad, hipStream_t s);
 // plan.frames: null for one frame, else plan.frames->n frames in one launch
-// (out / samples: frame 0's)
+// (out / samples: frame 0's).  variant: the packed template arguments of the
+// rc1pass_tile_kernel it launched (Rc1Variant::packed, option "rc1pass_variant");
+// left alone when nothing was launched
 hipError_t launch_rc1pass(const Ctx& c, const Rc1passArgs& a, bool phong, float4* out,
                           uint32_t* samples, unsigned long long* tile_samples, const int* order,
-                          uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s);
+                          uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s, int& variant);
 // after a frame: sums tile_samples into *total and/or builds the next LPT order
 hipError_t launch_tile_epilogue(uint32_t* tile_cost, unsigned long long* tile_samples,
                                 unsigned long long* total, const RenderPlan& plan, int* order,

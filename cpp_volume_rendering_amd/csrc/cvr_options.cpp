@@ -156,6 +156,8 @@ const Option kOptions[] = {
     // the last slice-based frame: slices drawn, and the launches that drew them
     {"sbtm_slices", nullptr, [](const Ctx* c) { return c->sbtm.slices; }, 1, 0, nullptr, nullptr, nullptr},
     {"sbtm_launches", nullptr, [](const Ctx* c) { return c->sbtm.launches; }, 1, 0, nullptr, nullptr, nullptr},
+    // the packed template arguments of the last rc1pass_tile_kernel launched (-1: none yet)
+    {"rc1pass_variant", nullptr, [](const Ctx* c) { return c->rc1pass_variant; }, 1, 0, nullptr, nullptr, nullptr},
     // the kept G-buffer's pixels with a hit (waits for its geometry pass; -1: none kept), and
     // the geometry launches so far
     {"deferred_hits", nullptr,

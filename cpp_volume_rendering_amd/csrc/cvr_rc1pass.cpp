@@ -604,7 +604,8 @@ static cvr_status render_rc1pass_frames(Ctx* c, const cvr_frame* frames, int nf,
 
   const bool phong = p->apply_gradient_shading != 0;
   st = timed_launch(c, s, [&] {
-    return cvr::launch_rc1pass(*c, A, phong, fo.d_out, fo.d_samples, fo.tile_samples, order, tile_cost, plan, s);
+    return cvr::launch_rc1pass(*c, A, phong, fo.d_out, fo.d_samples, fo.tile_samples, order, tile_cost, plan, s,
+                               c->rc1pass_variant);
   });
   if (st != CVR_OK) return st;
   const bool rebuild = order_rebuild_due(c, *os, vsig, views_close, order != nullptr) && tile_cost;

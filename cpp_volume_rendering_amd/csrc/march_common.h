@@ -151,30 +151,7 @@ __device__ __forceinline__ float pair_lerp(uint32_t w, float t) {
   return r;
 }
 
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// cvr_expf_neg (cvr_device.h) of two arguments at once, bit for bit: every multiply
-// and fma of the Cody-Waite reduction and the Horner polynomial is the same IEEE
-// operation on each half (v_pk_mul_f32 / v_pk_fma_f32: two lanes' worth per issue
-// slot on gfx950), only the rint, the conversion and the ldexp stay scalar.  For x
-// in [-86, 0] (the host's exp_fast range); ~17 instructions for two samples instead
-// of ~30.
-__device__ __forceinline__ f2v cvr_expf_neg2(f2v x) {
-  const f2v m = x * f2v{1.44269504088896341f, 1.44269504088896341f};
-  const float n0 = rintf(m.x), n1 = rintf(m.y);
-  const f2v n = {n0, n1};
-  f2v r = __builtin_elementwise_fma(n, f2v{-0.693359375f, -0.693359375f}, x);
-  r = __builtin_elementwise_fma(n, f2v{2.12194440e-4f, 2.12194440e-4f}, r);
-  f2v p = {1.9875691500e-4f, 1.9875691500e-4f};
-  p = __builtin_elementwise_fma(p, r, f2v{1.3981999507e-3f, 1.3981999507e-3f});
-  p = __builtin_elementwise_fma(p, r, f2v{8.3334519073e-3f, 8.3334519073e-3f});
-  p = __builtin_elementwise_fma(p, r, f2v{4.1665795894e-2f, 4.1665795894e-2f});
-  p = __builtin_elementwise_fma(p, r, f2v{1.6666665459e-1f, 1.6666665459e-1f});
-  p = __builtin_elementwise_fma(p, r, f2v{5.0000001201e-1f, 5.0000001201e-1f});
-  const f2v r2 = r * r;
-  const f2v v = __builtin_elementwise_fma(p, r2, r) + f2v{1.0f, 1.0f};
-  return f2v{ldexpf(v.x, (int)n0), ldexpf(v.y, (int)n1)};
-}
+typedef float f2v __attribute__((ext_vector_type(2)));   // trilerp_cell's packed y lerps
 
 // Skip flags of the density cells (precompute.hip: build_cell_flags, rebuilt
 // for every TF).  Densities are >= 0, so the 8 fp16 sign bits of a cell are

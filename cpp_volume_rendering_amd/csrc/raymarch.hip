@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 
 #include "cvr_device.h"
 #include "march_common.h"
@@ -32,12 +33,6 @@
 namespace cvr {
 
 constexpr int kQuadFlag = 1 << 28;   // order entry = tile | (quarter + 1) << 28 for quad tiles
-#ifdef CVR_PHONG_CLASSIFY_FULL
-constexpr bool kPhongClassifyFull = true;
-#else
-constexpr bool kPhongClassifyFull = false;
-#endif
-
 
 // Macro-cell skip.  The macro cell m (2^mshift texels a side) of a sample is
 // taken from its clamped texel coordinate exactly as sample_pos computes it; its
@@ -93,24 +88,6 @@ __device__ __forceinline__ bool skip_empty(const Rc1passArgs& A, const Ray& r, f
 //    of the last one (all empty), and m stays 2 steps short of the ray's end, so
 //    every skipped h is the full step.
 // Both leave the image and the sample count bit for bit as the plain march.
-
-// The composite's exp two samples per packed instruction (-DCVR_PAIR_EXP; DESIGN
-// §5‴): bit-exact and 45.7 -> 38.7 VALU per sample on the headline, but 4.7 %
-// slower (0.0731 -> 0.0765 ms per frame, A/B in one session, profiles/r06/s12-s13):
-// the march waits on dependencies, not on VALU issue.  Off by default.
-#ifdef CVR_PAIR_EXP
-constexpr bool kNoPairExp = false;
-#else
-constexpr bool kNoPairExp = true;
-#endif
-#ifndef CVR_PAIR_FROM
-#define CVR_PAIR_FROM 2
-#endif
-#ifndef CVR_RECOMPUTE_TF
-#define CVR_RECOMPUTE_TF 1
-#endif
-constexpr bool kRecomputeTf = CVR_RECOMPUTE_TF != 0;
-
 template <int K, bool PHONG, bool SKIP, int XF, int BUF, int FB, int CS>
 __device__ __forceinline__ void march_ray(const Rc1passArgs& A, const uint4* __restrict__ cells,
                                           const uint4* __restrict__ grad,
@@ -201,15 +178,7 @@ __device__ __forceinline__ void march_ray(const Rc1passArgs& A, const uint4* __r
       for (int j = 0; j < K; j++) {
         sp[j] = sample_pos(fmaf(r.dt.x, tj[j], r.o.x), fmaf(r.dt.y, tj[j], r.o.y),
                            fmaf(r.dt.z, tj[j], r.o.z), A);
-#ifdef CVR_PROBE_LDS_CELLS   // cost probe only: every sample from a 4 KiB LDS table (wrong images)
-        {
-          const uint4 v = reinterpret_cast<const uint4*>(tfp)[(sp[j].idx * 7u) & 255u];
-          raw[j] = make_uint4((v.x & 0x01ff01ffu) | 0x00000000u, (v.y & 0x01ff01ffu) | 0x00000000u,
-                              (v.z & 0x01ff01ffu) | 0x00000000u, (v.w & 0x01ff01ffu) | 0x00000000u);
-        }
-#else
         raw[j] = load_cell(sp[j]);
-#endif
       }
     } else {
 #pragma unroll
@@ -225,56 +194,30 @@ __device__ __forceinline__ void march_ray(const Rc1passArgs& A, const uint4* __r
     }
     // stage 2: density and transfer-function classification
     float4 src[K];
-    // Emission-absorption: alpha first (two 4-B LDS reads); the rgb lerps (two
-    // 16-B reads) only for visible samples, ~1 in 5 on the headline frame
+    // Alpha first (two 4-B LDS reads); the rgb lerps (two 16-B reads) only for
+    // visible samples, ~1 in 5 on the headline frame.  Blinn-Phong too: its
+    // shading needs the rgb only for the visible samples as well
     int tfi[K];
     float tfa[K];
-    float txd[K];   // kPairExp: the TF coordinate, its index and weight recomputed at the rgb lerps
     // we[j], wave-uniform: sample j of every marching lane lies in an empty cell.
     // Each is tested right before its sample's math, so the loads of the later
     // samples stay in flight behind it (testing all four first waited for all).
     bool we[K];
     int qlast = 0;   // the last sample's skip distance (0: no skip), read before raw[] dies
-    // Blinn-Phong too (CVR_PHONG_CLASSIFY_FULL: the round-3 full classify of every
-    // sample): its shading needs the rgb only for the visible samples as well
-    constexpr bool kAlphaFirst = !PHONG || !kPhongClassifyFull;
-    if (kAlphaFirst) {
 #pragma unroll
-      for (int j = 0; j < K; j++) {
-        we[j] = CS > 0 && __ballot(!cell_empty(raw[j])) == 0;
-        if (CS >= 2 && j == K - 1) qlast = cell_empty(raw[j]) ? cell_skip_q(raw[j]) : 0;
-        if (CS > 0 && we[j]) {
-          tfa[j] = 0.0f; tfi[j] = 0; txd[j] = 0.0f; src[j].w = 0.0f;
-        } else {
-          const float xd = fmaf(trilerp_cell<!PHONG>(raw[j], sp[j].ax, sp[j].ay, sp[j].az), fn, -0.5f);
-          tfa[j] = filter_weight<FB>(__builtin_amdgcn_fractf(xd));   // see classify
-          tfi[j] = cvt_flr(xd) + 1;
-          txd[j] = xd;
-          src[j].w = lerpf(tfp[tfi[j]].w, tfp[tfi[j] + 1].w, tfa[j]);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < K; j++) {
-        we[j] = CS > 0 && __ballot(!cell_empty(raw[j])) == 0;
-        if (CS >= 2 && j == K - 1) qlast = cell_empty(raw[j]) ? cell_skip_q(raw[j]) : 0;
-        if (CS > 0 && we[j]) src[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        else src[j] = classify<FB>(tfp, fn, trilerp_cell(raw[j], sp[j].ax, sp[j].ay, sp[j].az));
+    for (int j = 0; j < K; j++) {
+      we[j] = CS > 0 && __ballot(!cell_empty(raw[j])) == 0;
+      if (CS >= 2 && j == K - 1) qlast = cell_empty(raw[j]) ? cell_skip_q(raw[j]) : 0;
+      if (CS > 0 && we[j]) {
+        tfa[j] = 0.0f; tfi[j] = 0; src[j].w = 0.0f;
+      } else {
+        const float xd = fmaf(trilerp_cell<!PHONG>(raw[j], sp[j].ax, sp[j].ay, sp[j].az), fn, -0.5f);
+        tfa[j] = filter_weight<FB>(__builtin_amdgcn_fractf(xd));   // see classify
+        tfi[j] = cvt_flr(xd) + 1;
+        src[j].w = lerpf(tfp[tfi[j]].w, tfp[tfi[j] + 1].w, tfa[j]);
       }
     }
     bool visible = false;
-    // Alphas two samples per packed exp (cvr_expf_neg2, the same bits as the scalar
-    // cvr_expf_neg): a_j depends on sample j's extinction only, not on the
-    // composite before it, so at each even j the pair (j, j+1) is computed when some
-    // lane of the wave may composite either of them (empty space skips it, as the
-    // composite's branches do).  Computed at the pair rather than for the whole
-    // batch up front, which held four more registers across the composite and
-    // spilled (13 VGPRs, 0.073 -> 0.080 ms per frame).
-    constexpr bool kPairExp = XF == 1 && kAlphaFirst && (K % 2 == 0) && !kNoPairExp;
-    float a_odd = 0.0f;   // the pair's second alpha, used by the next sample
-    // the samples from kPairFrom on go in pairs (the first ones keep the scalar exp:
-    // at j = 0 the batch's registers peak)
-    constexpr int kPairFrom = CVR_PAIR_FROM;
 #ifdef CVR_PROBE_SHADE_PASSES   // cost probe (tools/phong_pass_probe.py): shading passes per batch
     bool shj[K];
     if (PHONG) {
@@ -295,16 +238,6 @@ __device__ __forceinline__ void march_ray(const Rc1passArgs& A, const uint4* __r
     // 1.4x slower on the headline frame).
 #pragma unroll
     for (int j = 0; j < K; j++) {
-      float a_even = 0.0f;
-      if (kPairExp && j >= kPairFrom && ((j - kPairFrom) & 1) == 0) {
-        const bool may = !done && ((vj[j] && !(CS > 0 && we[j]) && src[j].w > 0.0f) ||
-                                   (vj[j + 1] && !(CS > 0 && we[j + 1]) && src[j + 1].w > 0.0f));
-        if (__ballot(may) != 0) {
-          const f2v e = cvr_expf_neg2(f2v{-(src[j].w * hj[j]), -(src[j + 1].w * hj[j + 1])});
-          a_even = 1.0f - e.x;
-          a_odd = 1.0f - e.y;
-        }
-      }
       if (!done) {
         if (!vj[j]) {
           done = true;
@@ -313,16 +246,11 @@ __device__ __forceinline__ void march_ray(const Rc1passArgs& A, const uint4* __r
           float4 sc = src[j];
           if (!(CS > 0 && we[j]) && sc.w > 0.0f) {
             visible = true;
-            if (kAlphaFirst) {   // classify's rgb, same lerps
-              // (kPairExp: index and weight again from the coordinate -- two VALU per
-              // visible sample for two registers fewer per batch sample across the composite)
-              const int ti = kPairExp && kRecomputeTf ? cvt_flr(txd[j]) + 1 : tfi[j];
-              const float ta = kPairExp && kRecomputeTf ? filter_weight<FB>(__builtin_amdgcn_fractf(txd[j])) : tfa[j];
-              const float4 t0 = tfp[ti], t1 = tfp[ti + 1];
-              sc.x = lerpf(t0.x, t1.x, ta);
-              sc.y = lerpf(t0.y, t1.y, ta);
-              sc.z = lerpf(t0.z, t1.z, ta);
-            }
+            // classify's rgb, same lerps
+            const float4 t0 = tfp[tfi[j]], t1 = tfp[tfi[j] + 1];
+            sc.x = lerpf(t0.x, t1.x, tfa[j]);
+            sc.y = lerpf(t0.y, t1.y, tfa[j]);
+            sc.z = lerpf(t0.z, t1.z, tfa[j]);
             if (PHONG) {
               shade_phong(A, grad, sp[j], r.dir, tj[j], r.tpos, hg, eye, sc);
               nshade++;
@@ -331,8 +259,7 @@ __device__ __forceinline__ void march_ray(const Rc1passArgs& A, const uint4* __r
 #endif
             }
             const float x = -(sc.w * hj[j]);
-            const float a = (kPairExp && j >= kPairFrom) ? (((j - kPairFrom) & 1) ? a_odd : a_even)
-                                     : 1.0f - (XF == 2 ? cvr_expf_native(x) : XF ? cvr_expf_neg(x) : cvr_expf_nb(x));
+            const float a = 1.0f - (XF == 2 ? cvr_expf_native(x) : XF ? cvr_expf_neg(x) : cvr_expf_nb(x));
             const float om = 1.0f - dst.w;
             dst.x = fmaf(om, sc.x * a, dst.x);
             dst.y = fmaf(om, sc.y * a, dst.y);
@@ -923,14 +850,73 @@ __global__ void clear_u32_kernel(uint32_t* __restrict__ p, int n) {
 // Launchers
 // ---------------------------------------------------------------------------
 
-// Kernel variant: K (batch), PHONG, SKIP (empty-space skipping compiled in),
-// QUAD (quad path compiled in), XF (exp: 0 CVR-SPEC, 1 CVR-SPEC without range
-// selects, 2 the native v_exp_f32 -- tolerance mode, option native_exp).  Paths a frame does not
-// use are compiled out: they would cost the hot loop registers (occupancy).
-template <int K, bool PHONG, bool SKIP, bool QUAD, int XF, int BUF, int FB = 0, int CS = 0>
+// Kernel variant, the template arguments of rc1pass_tile_kernel: K (batch), PHONG,
+// SKIP (macro-cell empty-space skipping compiled in), QUAD (quad path compiled
+// in), XF (exp: 0 CVR-SPEC, 1 CVR-SPEC without range selects, 2 the native
+// v_exp_f32 -- tolerance mode, option native_exp), BUF (cell addressing: 0 64-bit,
+// 1 buffer offsets, 2 their 24-bit multiply-add form), FB (filter_bits), CS
+// (cell_skip).  Paths a frame does not use are compiled out: they would cost the
+// hot loop registers (occupancy).
+struct Rc1Variant {
+  int K, phong, skip, quad, xf, buf, fb, cs;
+  constexpr int packed() const {   // option "rc1pass_variant" (include/cvr.h)
+    return K | phong << 4 | skip << 5 | quad << 6 | xf << 8 | buf << 10 | fb << 12 | cs << 16;
+  }
+};
+
+// The variants that are compiled, in families: each row is built for K 2 and 4,
+// with and without PHONG, every BUF in [buf_lo, buf_hi] and every XF in [xf_lo,
+// xf_hi]: kRc1Variants, 212 kernels (the product of the eight arguments' ranges
+// would be 1440).  SKIP takes two rows per family because the rows, expanded in
+// this order with the higher BUF and XF first, are the order of the kernels in
+// the code object, which is kept as it was.
+struct Rc1Family { int skip, quad, fb, cs, buf_lo, buf_hi, xf_lo, xf_hi; };
+constexpr Rc1Family kRc1Families[] = {
+    // SKIP QUAD FB CS  BUF   XF
+    {1, 0, 8, 0, 0, 2, 0, 1},   // texture-unit weights (filter_bits 8), macro-cell skip
+    {0, 0, 0, 3, 2, 2, 2, 2},   // tolerance mode (native_exp): the headline's variant only, DESIGN §5‴
+    {0, 0, 0, 1, 0, 2, 0, 1},   // per-cell skip 1, 3, 4, 2
+    {0, 0, 0, 3, 0, 2, 0, 1},
+    {0, 0, 0, 4, 0, 2, 0, 1},
+    {0, 0, 0, 2, 0, 2, 0, 1},
+    {1, 1, 0, 0, 0, 0, 0, 1},   // quad march (64-bit addresses only), macro-cell skip
+    {1, 0, 0, 0, 0, 2, 0, 1},   // macro-cell skip
+    {0, 0, 8, 0, 0, 2, 0, 1},   // texture-unit weights
+    {0, 1, 0, 0, 0, 0, 0, 1},   // quad march
+    {0, 0, 0, 0, 0, 2, 0, 1},   // no skip
+};
+struct Rc1VariantList { Rc1Variant v[256]; int n; };
+constexpr Rc1VariantList rc1_variant_list() {
+  Rc1VariantList l{};
+  for (int K = 2; K <= 4; K += 2)
+    for (int phong = 1; phong >= 0; phong--)
+      for (const Rc1Family& f : kRc1Families)
+        for (int buf = f.buf_hi; buf >= f.buf_lo; buf--)
+          for (int xf = f.xf_hi; xf >= f.xf_lo; xf--)
+            l.v[l.n++] = Rc1Variant{K, phong, f.skip, f.quad, xf, buf, f.fb, f.cs};
+  return l;
+}
+constexpr Rc1VariantList kRc1Variants = rc1_variant_list();
+static_assert(kRc1Variants.n == 212, "the rc1pass_tile_kernel instantiations (DESIGN.md, compile time)");
+
+// Where v stands in kRc1Variants, or -1: not compiled.
+constexpr int rc1_variant_index(const Rc1Variant& v) {
+  if (v.K != 2 && v.K != 4) return -1;
+  int i = ((v.K == 4 ? 2 : 0) + (v.phong ? 0 : 1)) * (kRc1Variants.n / 4);
+  for (const Rc1Family& f : kRc1Families) {
+    const int nx = f.xf_hi - f.xf_lo + 1;
+    if (f.skip == v.skip && f.quad == v.quad && f.fb == v.fb && f.cs == v.cs && v.buf >= f.buf_lo &&
+        v.buf <= f.buf_hi && v.xf >= f.xf_lo && v.xf <= f.xf_hi)
+      return i + (f.buf_hi - v.buf) * nx + (f.xf_hi - v.xf);
+    i += (f.buf_hi - f.buf_lo + 1) * nx;
+  }
+  return -1;
+}
+
+template <int K, bool PHONG, bool SKIP, bool QUAD, int XF, int BUF, int FB, int CS>
 static hipError_t launch_variant(const Ctx& c, const Rc1passArgs& a, float4* out, uint32_t* samples,
                                  unsigned long long* tile_samples, const int* order,
-                                 uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s) {
+                                 uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s, int& variant) {
   size_t lds = (size_t)(a.tf_n + 2) * sizeof(float4);
   if (c.max_waves_cu > 0) lds = std::max(lds, (size_t)(160 * 1024 / c.max_waves_cu) & ~(size_t)255);
   // cell (1,1,1) <-> texel (0,0,0)
@@ -953,84 +939,77 @@ static hipError_t launch_variant(const Ctx& c, const Rc1passArgs& a, float4* out
   hipLaunchKernelGGL((rc1pass_tile_kernel<K, PHONG, SKIP, QUAD, XF, BUF, FB, CS>), dim3(grid / WG), dim3(64 * WG), lds, s,
                      a, cells, (const uint4*)c.d_grad, (const float4*)c.d_tf, out, samples,
                      tile_samples, order, tile_cost, order ? plan.boost : 0, lf);
-  return hipGetLastError();
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) variant = Rc1Variant{K, PHONG, SKIP, QUAD, XF, BUF, FB, CS}.packed();
+  return e;
 }
 
-template <int K, bool PHONG, bool SKIP>
-static hipError_t launch_kps(const Ctx& c, const Rc1passArgs& a, float4* out, uint32_t* samples,
-                             unsigned long long* ts, const int* order, uint32_t* tile_cost,
-                             const RenderPlan& plan, hipStream_t s) {
-  // buffer loads address the cell grid with 32-bit byte offsets (BUF 2: the
-  // 24-bit multiply-add form, while 16 * pitch_z < 2^23, i.e. up to 723^3)
+// Which variant a frame takes.  K and SKIP hold for every frame; the rest by the
+// first row that matches, with
+//   buf   0 for a cell grid of 4 GiB or more; else 2 while 16 * pitch_z fits the
+//         24-bit multiply-add (< 2^23, i.e. up to 723^3); else 1
+//   exp   1 while every sample's extinction stays in exp's fast range
+//         (a.exp_fast, fill_frame_args); else 0
+//
+//   K     2 with option batch 2, or batch 0 (auto) and gradient shading; else 4
+//   SKIP  the macro cells' occupancy is bound (a.occ: options macro and
+//         skip_min_pct, and only while the per-cell skip is off)
+//
+//   frame                                  QUAD  FB  CS            BUF  XF
+//   filter_bits 8                           0    8   0             buf  exp     (native_exp ignored)
+//   no SKIP, no quad, a.cell_skip > 0       0    0   a.cell_skip*  buf  exp**
+//   quad: an order and plan.quad_pct > 0    1    0   0             0    exp
+//   otherwise                               0    0   0             buf  exp
+//   *  1, 3 or 4; any other value acts as 2
+//   ** 2 with native_exp, at buf 2 and cell_skip 3 only (kRc1Families has no other)
+static Rc1Variant rc1_resolve_variant(const Ctx& c, const Rc1passArgs& a, bool phong, const int* order,
+                                      const RenderPlan& plan) {
   const int buf = c.cells_bytes >= (size_t(1) << 32) ? 0
                   : (c.cells.bpitch_z > 0 && c.cells.bpitch_z < (1 << 23)) ? 2 : 1;
-  if (a.filter_bits == 8) {   // GL texture-unit weights: the ray-parallel march only
-    if (buf == 2)
-      return a.exp_fast ? launch_variant<K, PHONG, SKIP, false, true, 2, 8>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                        : launch_variant<K, PHONG, SKIP, false, false, 2, 8>(c, a, out, samples, ts, order, tile_cost, plan, s);
-    if (buf == 1)
-      return a.exp_fast ? launch_variant<K, PHONG, SKIP, false, true, 1, 8>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                        : launch_variant<K, PHONG, SKIP, false, false, 1, 8>(c, a, out, samples, ts, order, tile_cost, plan, s);
-    return a.exp_fast ? launch_variant<K, PHONG, SKIP, false, true, 0, 8>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                      : launch_variant<K, PHONG, SKIP, false, false, 0, 8>(c, a, out, samples, ts, order, tile_cost, plan, s);
-  }
   const bool quad = order && plan.quad_pct > 0;
-  if (!SKIP && !quad && a.cell_skip > 0) {   // per-cell skip flags (a.occ is null then)
-#define CVR_CS_LAUNCH(CSV)                                                                                 \
-    if (buf == 2)                                                                                          \
-      return a.exp_fast ? launch_variant<K, PHONG, false, false, true, 2, 0, CSV>(c, a, out, samples, ts, order, tile_cost, plan, s) \
-                        : launch_variant<K, PHONG, false, false, false, 2, 0, CSV>(c, a, out, samples, ts, order, tile_cost, plan, s); \
-    if (buf == 1)                                                                                          \
-      return a.exp_fast ? launch_variant<K, PHONG, false, false, true, 1, 0, CSV>(c, a, out, samples, ts, order, tile_cost, plan, s) \
-                        : launch_variant<K, PHONG, false, false, false, 1, 0, CSV>(c, a, out, samples, ts, order, tile_cost, plan, s); \
-    return a.exp_fast ? launch_variant<K, PHONG, false, false, true, 0, 0, CSV>(c, a, out, samples, ts, order, tile_cost, plan, s) \
-                      : launch_variant<K, PHONG, false, false, false, 0, 0, CSV>(c, a, out, samples, ts, order, tile_cost, plan, s);
-    // tolerance mode (option native_exp): the headline's variants only (buffer
-    // addressing, exact weights, cell skip 3, either shading) -- DESIGN §5‴
-    if (a.exp_native && buf == 2 && a.cell_skip == 3)
-      return launch_variant<K, PHONG, false, false, 2, 2, 0, 3>(c, a, out, samples, ts, order, tile_cost, plan, s);
-    if (a.cell_skip == 1) { CVR_CS_LAUNCH(1) }
-    if (a.cell_skip == 3) { CVR_CS_LAUNCH(3) }
-    if (a.cell_skip == 4) { CVR_CS_LAUNCH(4) }
-    CVR_CS_LAUNCH(2)
-#undef CVR_CS_LAUNCH
+  Rc1Variant v{};
+  v.K = (c.batch == 2 || (c.batch == 0 && phong)) ? 2 : 4;
+  v.phong = phong;
+  v.skip = a.occ != nullptr;
+  v.xf = a.exp_fast ? 1 : 0;
+  v.buf = buf;
+  if (a.filter_bits == 8) {
+    v.fb = 8;
+  } else if (!v.skip && !quad && a.cell_skip > 0) {
+    v.cs = (a.cell_skip == 1 || a.cell_skip == 3 || a.cell_skip == 4) ? a.cell_skip : 2;
+    if (a.exp_native && buf == 2 && a.cell_skip == 3) v.xf = 2;
+  } else if (quad) {
+    v.quad = 1;
+    v.buf = 0;
   }
-  if (quad)
-    return a.exp_fast ? launch_variant<K, PHONG, SKIP, true, true, 0>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                      : launch_variant<K, PHONG, SKIP, true, false, 0>(c, a, out, samples, ts, order, tile_cost, plan, s);
-  if (buf == 2)
-    return a.exp_fast ? launch_variant<K, PHONG, SKIP, false, true, 2>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                      : launch_variant<K, PHONG, SKIP, false, false, 2>(c, a, out, samples, ts, order, tile_cost, plan, s);
-  if (buf == 1)
-    return a.exp_fast ? launch_variant<K, PHONG, SKIP, false, true, 1>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                      : launch_variant<K, PHONG, SKIP, false, false, 1>(c, a, out, samples, ts, order, tile_cost, plan, s);
-  return a.exp_fast ? launch_variant<K, PHONG, SKIP, false, true, 0>(c, a, out, samples, ts, order, tile_cost, plan, s)
-                    : launch_variant<K, PHONG, SKIP, false, false, 0>(c, a, out, samples, ts, order, tile_cost, plan, s);
+  return v;
 }
 
-template <int K, bool PHONG>
-static hipError_t launch_kp(const Ctx& c, const Rc1passArgs& a, float4* out, uint32_t* samples,
-                            unsigned long long* ts, const int* order, uint32_t* tile_cost,
-                            const RenderPlan& plan, hipStream_t s) {
-  return a.occ ? launch_kps<K, PHONG, true>(c, a, out, samples, ts, order, tile_cost, plan, s)
-               : launch_kps<K, PHONG, false>(c, a, out, samples, ts, order, tile_cost, plan, s);
+// One launcher per compiled variant, in their order (which is also the order the
+// kernels are instantiated in): a frame's launch is an index and an indirect call.
+using Rc1Launcher = decltype(&launch_variant<4, false, false, false, 1, 2, 0, 3>);
+template <int I>
+constexpr Rc1Launcher rc1_launcher() {
+  constexpr Rc1Variant V = kRc1Variants.v[I];
+  static_assert(rc1_variant_index(V) == I, "kRc1Variants and rc1_variant_index disagree");
+  return &launch_variant<V.K, V.phong != 0, V.skip != 0, V.quad != 0, V.xf, V.buf, V.fb, V.cs>;
 }
-
-template <int K>
-static hipError_t launch_k(const Ctx& c, const Rc1passArgs& a, bool phong, float4* out,
-                           uint32_t* samples, unsigned long long* ts, const int* order,
-                           uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s) {
-  return phong ? launch_kp<K, true>(c, a, out, samples, ts, order, tile_cost, plan, s)
-               : launch_kp<K, false>(c, a, out, samples, ts, order, tile_cost, plan, s);
-}
+template <class Seq>
+struct Rc1Launchers;
+template <int... I>
+struct Rc1Launchers<std::integer_sequence<int, I...>> {
+  static constexpr Rc1Launcher at[sizeof...(I)] = {rc1_launcher<I>()...};
+};
 
 hipError_t launch_rc1pass(const Ctx& c, const Rc1passArgs& a, bool phong, float4* out,
                           uint32_t* samples, unsigned long long* tile_samples, const int* order,
-                          uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s) {
+                          uint32_t* tile_cost, const RenderPlan& plan, hipStream_t s, int& variant) {
   if (a.ntiles <= 0) return hipSuccess;
   if (a.tf_n > kMaxTfLds) return hipErrorInvalidValue;
-  if (c.batch == 2 || (c.batch == 0 && phong)) return launch_k<2>(c, a, phong, out, samples, tile_samples, order, tile_cost, plan, s);
-  return launch_k<4>(c, a, phong, out, samples, tile_samples, order, tile_cost, plan, s);
+  const int i = rc1_variant_index(rc1_resolve_variant(c, a, phong, order, plan));
+  if (i < 0) return hipErrorInvalidValue;   // not a compiled variant: nothing is launched
+  return Rc1Launchers<std::make_integer_sequence<int, kRc1Variants.n>>::at[i](c, a, out, samples, tile_samples, order,
+                                                                             tile_cost, plan, s, variant);
 }
 
 hipError_t launch_tile_epilogue(uint32_t* tile_cost, unsigned long long* tile_samples,

@@ -346,6 +346,14 @@ cvr_status  cvr_set_stream(cvr_ctx* ctx, void* hip_stream);
  *                cvr_render_dosct likewise takes the CONSIDER_BORDERS attenuation of
  *                an outside cone tap through v_exp_f32 (its march, counts and ERT
  *                stay bit-exact).  Default 0.
+ *   "rc1pass_variant" (read-only) which of the ray-march kernel's compiled variants the
+ *                context's most recent cvr_render_rc1pass[_frames] launched, -1 before the
+ *                first: bits 0-3 K (samples per batch, 2 or 4), bit 4 gradient shading,
+ *                bit 5 macro-cell skip, bit 6 quad march, bits 8-9 exp (0 CVR-SPEC, 1 the
+ *                same without range selects, 2 native), bits 10-11 cell addressing (0
+ *                64-bit, 1 buffer offsets, 2 the 24-bit multiply-add form), bits 12-15
+ *                filter_bits, bits 16-18 cell_skip.  What the options above resolve to
+ *                for the frame (raymarch.hip rc1_resolve_variant holds the rules).
  * One option changes the arithmetic (and so the image) rather than the speed:
  *   "filter_bits" 0: exact float GL_LINEAR weights (CVR-SPEC, the default);
  *                8: every GL_LINEAR weight (volume, gradient, TF; ray_marching_1p.comp:133,

@@ -55,7 +55,8 @@ RANGES = {
 FLAGS = {"shade_counters": 0, "tile_stats": 0}     # any value, stored as 0 / 1
 READ_ONLY = {"cell_flags_active": 0, "cell_flags_valid": 0, "sat_build_us": 0,
              "occ_empty_permille": -1,             # -1 until a render has built the occupancy
-             "flat_cap_kjobs": 0, "light_cache_builds": 0}
+             "flat_cap_kjobs": 0, "light_cache_builds": 0,
+             "rc1pass_variant": -1}                # -1 until cvr_render_rc1pass has launched its kernel
 
 
 @pytest.fixture(scope="module")

@@ -80,7 +80,7 @@ L_BOX = _find("if (wave_in_box) {", L_S1)
 L_S2 = _find("// stage 2:", L_BOX)
 L_VIS = _find("bool visible = false;", L_S2)
 L_S3 = _find("// stage 3:", L_VIS)
-L_RGB = _find("if (kAlphaFirst) {   // classify's rgb", L_S3)
+L_RGB = _find("// classify's rgb", L_S3)
 L_X = _find("const float x = -(sc.w * hj[j]);", L_RGB)
 L_OM = _find("const float om = 1.0f - dst.w;", L_X)
 L_SS = _find("s = ss;", L_OM)
@@ -95,7 +95,7 @@ def march_cat(line):
     if L_S2 <= line < L_VIS:
         return "classify: trilinear + TF alpha"
     if L_VIS <= line < L_S3:
-        return "composite: exp of the batch (packed pairs)"
+        return "shade-pass probe (CVR_PROBE_SHADE_PASSES builds only)"
     if L_RGB <= line < L_X:
         return "composite: TF rgb (visible samples)"
     if L_X <= line < L_OM:
@@ -179,8 +179,6 @@ def category(f, line, lm):
     c = FUNC_CAT.get(fn)
     if fn in FUNC_CAT and c is not None:
         return c
-    if fn == "cvr_expf_neg2":
-        return "composite: exp of the batch (packed pairs)"
     if fn and fn.startswith("cvr_expf"):
         return "composite: exp"
     return march_cat(lm) if lm else f"{f}:{fn}"
